@@ -1,6 +1,7 @@
 """Benchmark: whole-node frames/s of the per-frame multi-task hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config full|yolo_face|yolo_raw|vitpose] [--batch B]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N ...
 
@@ -23,7 +24,13 @@ starts N child processes (one per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, 
 BEFORE it touches the GPU, waits for them and exits with their status; rank 0 prints the line.
 Under torchrun the ranks come from the environment.
 
-Rank 0 prints ONE JSON line. Extra objects:
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps and prints the
+line (``value``, ``ms_per_step`` = milliseconds per timed step); its ``roofline``, ``cpu_baseline``
+and ``parity`` are null. ``--dump-outputs DIR`` writes what the last timed step returned (every
+tensor of the step's result, rank 0's) as DIR/<name>.npy in float32 (float64 for 64-bit values),
+at most 60 MB in all: an array over its share of that is cut to a fixed, seeded sample of its
+elements. The inputs are seeded, so two builds run with the same arguments dump comparable files.
+``--full`` adds the legs that take runs of their own; the extra objects it fills in:
   roofline     — the dominant kernel of the config, timed with HIP events on its stream
                  (isolated pass right after the timed region when the heads run concurrently;
                  its in-region, co-resident time is reported beside it); achieved = its
@@ -89,6 +96,11 @@ def parse():
     ap.add_argument("--sequential-heads", action="store_true",
                     help="enqueue the three heads on one stream (default: one HIP stream per head)")
     ap.add_argument("--dominant", default="", help="pack name(s) timed for the roofline (comma list)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline of the dominant kernel, the CPU baseline and the parity "
+                         "against the oracle (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -203,7 +215,7 @@ def main():
             o = model.forward_all(x, face_stride=STRIDE, concurrent=not args.sequential_heads)
             dets, cnt = non_max_suppression_padded(o["det"])
             coords, scores = ops.softargmax(o["heatmaps"])
-            o.update(dets=dets, cnt=cnt, coords=coords)
+            o.update(dets=dets, cnt=cnt, coords=coords, scores=scores)
             if ws > 1:
                 # one RCCL all-gather over xGMI of each frame's record: detections + count,
                 # embedding + norm, keypoints + scores (prpe/dist.py)
@@ -224,7 +236,7 @@ def main():
         else:
             heat = model.vitpose_from_pixels(x).heatmaps
             coords, scores = ops.softargmax(heat)
-            o = {"heatmaps": heat, "coords": coords}
+            o = {"heatmaps": heat, "coords": coords, "scores": scores}
             if ws > 1:
                 gather_tensor(torch.cat([coords, scores[..., None]], -1))
         return o
@@ -232,7 +244,7 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    eng.watch = set(dominant)
+    eng.watch = set(dominant) if args.full else set()
     eng.events = {}
     if ws > 1:
         dist.barrier()
@@ -250,6 +262,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     fps = B * ws * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, o)
 
     # ---- roofline of the dominant kernel. With the heads on their own streams the dominant
     # launch shares the CUs with the other heads' kernels, so its event time inside the timed
@@ -259,7 +273,7 @@ def main():
         return [a.elapsed_time(b) for a, b, *_ in evs]
 
     timed = [m for d in dominant for m in ev_ms(eng.events.get(d, []))]
-    isolated = cfg == "full" and not args.sequential_heads
+    isolated = args.full and cfg == "full" and not args.sequential_heads
     if isolated:
         eng.events = {}
         eng.watch = set(dominant)
@@ -320,13 +334,13 @@ def main():
 
     # ---- parity on frames spread over the batch + CPU baseline, rank 0, N = 1 only
     cpu = parity = None
-    if rank == 0 and not args.no_cpu_baseline and ws == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and ws == 1:
         parity, cpu = cpu_legs(cfg, sd, x, o, B, args.cpu_reps)
     # ---- N > 1 (full config): rank 0 checks the records the timed region's all-gather delivered
     # for sampled frames of EVERY rank's shard against the oracle on those frames (regenerated
     # from the rank's input seed); each rank contributes its sampled frames' raw det rows (one
     # more small all-gather, outside the timed region) so NMS exactness is checked on them
-    if ws > 1 and cfg == "full" and not args.no_cpu_baseline:
+    if args.full and ws > 1 and cfg == "full" and not args.no_cpu_baseline:
         det_samples = gather_tensor(o["det"][sample_local(B)].contiguous())
         if rank == 0:
             from oracle import model_ref as R
@@ -351,6 +365,34 @@ def main():
         print(json.dumps(line), flush=True)
     if ws > 1:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET = 60 * 10 ** 6       # bytes of array data per --dump-outputs directory
+
+
+def dump_outputs(dirname, o, seed=0):
+    """DIR/<name>.npy for every tensor of the step's result ``o`` (a list under ``name`` becomes
+    name_0, name_1, ...): float32, or float64 for 64-bit values. The arrays share DUMP_BUDGET,
+    smallest first; one over its share is written as a 1-d sample of its flattened elements at
+    sorted positions drawn once from ``seed`` (the same positions in every run)."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for k, v in o.items():
+        for i, t in enumerate(v) if isinstance(v, (list, tuple)) else [(None, v)]:
+            arrays[k if i is None else f"{k}_{i}"] = t
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET
+    order = sorted(arrays, key=lambda k: arrays[k].numel())
+    for n, k in enumerate(order):
+        t = arrays[k].detach()
+        a = t.cpu().numpy().astype(np.float64 if t.dtype in (torch.float64, torch.int64) else np.float32)
+        share = left // (len(order) - n)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def sample_local(B: int) -> list[int]:

@@ -305,6 +305,37 @@ def test_traffic_records_name_their_kernel_sources():
         assert h != bench.kernel_sources_hash(), "a subset hash must differ from the all-sources hash"
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: one <name>.npy per tensor of the step's result (lists numbered),
+    float32 (float64 for 64-bit values); within the byte budget the arrays are whole, over it
+    the largest is cut to the same sorted sample of its elements in every run."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    o = {"heat": torch.rand(7, 5, 11, generator=g), "cnt": torch.arange(9, dtype=torch.int32),
+         "idx": torch.arange(4, dtype=torch.int64) + 2 ** 40, "gathered": [torch.rand(3, 2, generator=g), torch.ones(2)]}
+    a_dir, b_dir, c_dir = (str(tmp_path / n) for n in "abc")
+    bench.dump_outputs(a_dir, o)
+    assert sorted(os.listdir(a_dir)) == ["cnt.npy", "gathered_0.npy", "gathered_1.npy", "heat.npy", "idx.npy"]
+    heat = np.load(os.path.join(a_dir, "heat.npy"))
+    assert heat.dtype == np.float32 and np.array_equal(heat, o["heat"].numpy())
+    assert np.load(os.path.join(a_dir, "cnt.npy")).dtype == np.float32
+    idx = np.load(os.path.join(a_dir, "idx.npy"))
+    assert idx.dtype == np.float64 and np.array_equal(idx, o["idx"].numpy().astype(np.float64))
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 600)          # heat (1540 bytes) no longer fits
+    bench.dump_outputs(b_dir, o)
+    bench.dump_outputs(c_dir, o)
+    files = [np.load(os.path.join(b_dir, f)) for f in sorted(os.listdir(b_dir))]
+    assert len(files) == 5 and sum(f.nbytes for f in files) <= 600
+    cut = np.load(os.path.join(b_dir, "heat.npy"))
+    assert cut.ndim == 1 and 0 < cut.size < heat.size and np.array_equal(cut, np.load(os.path.join(c_dir, "heat.npy")))
+    assert np.isin(cut, heat).all()
+    assert np.array_equal(np.load(os.path.join(b_dir, "gathered_0.npy")), o["gathered"][0].numpy())
+
+
 def test_weight_versions_trigger_repack(monkeypatch):
     """Host logic of the stale-weights guard (prpe/model.py ``_sync_weights``) without a GPU:
     the engine is a stub counting repacks; in-place writes through the branch trees'

@@ -92,7 +92,7 @@ case "$cmd" in
   evidence_bench)
     R=$1; [ -n "$R" ] || { echo "evidence needs the round tag (e.g. r04)"; exit 9; }
     for C in full yolo_face vitpose yolo_raw; do
-      timeout -k 10 400 python bench.py --config $C --steps 20 --warmup 3 > $O/${R}_bench_${C}.json 2> $O/${R}_bench_${C}.err || exit 17
+      timeout -k 10 400 python bench.py --full --config $C --steps 20 --warmup 3 > $O/${R}_bench_${C}.json 2> $O/${R}_bench_${C}.err || exit 17
       tail -c 300 $O/${R}_bench_${C}.json
     done ;;
   py)
