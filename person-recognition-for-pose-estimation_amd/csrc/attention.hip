@@ -1,19 +1,18 @@
 // Attention kernels.
 //
-// prpe_attention — ViTPose-B self-attention (L = 192 tokens, D = 64, 12 heads), one
-// workgroup per (frame, head), one wave per 16-query tile (12 waves = 768 threads).
-// K and V of the head are staged once in LDS as split-bf16 (hi, lo) planes; V is stored
-// transposed so its B-fragments are contiguous. S = Q K^T and O = P V run on
+// prpe_attention — ViTPose-B self-attention (L = 192 tokens, D = 64, 12 heads), one wave per
+// 16-query tile (12 waves = 768 threads), a workgroup per group of heads of one frame. K and
+// V^T are staged in LDS as split-bf16 (hi, lo) planes; S and O run on
 // v_mfma_f32_16x16x32_bf16 with the 3-pass split (lo*hi + hi*lo + hi*hi), fp32 softmax in
-// registers (row = 4*(lane>>4)+r of the 16x16 accumulator, 16 lanes per row), P re-staged
-// through a per-wave LDS slab 32 keys at a time as the A operand of PV.
+// registers. Two kernels: the whole-head kernel (the default) and the streaming kernel for
+// frames a 32-bit buffer offset cannot span. (The round-1 kernel with P through LDS and the
+// round-2 per-head chunked kernel: tools/exp/attention_v1_v2.patch.)
 // Reference: eager_attention_forward (modeling_vitpose_backbone.py:100-126):
 //   softmax(matmul(q, k^T) * scaling) @ v.
 //
 // prpe_psa_attention — YOLO v11 PSA attention core (nn.py:111-122), 25 tokens, 2 heads;
 // tiny, VALU fp32, one workgroup per frame.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -24,146 +23,10 @@ constexpr int AD = 64;         // head dim
 // fg + 1 (MI355X_MICROARCH.md, LDS); with 10 slots per row the first set lands on the even
 // slots and the second on the odd ones: conflict-free (the 144-B pitch was 2-way)
 constexpr int KROW = AD + 16;
-constexpr int VROW = AL + 8;   // bf16 per V^T row in LDS (pad 16 B)
 constexpr int NWAVE = AL / 16; // 12
 
-__global__ __launch_bounds__(NWAVE * 64) void vit_attention_kernel(const float* __restrict__ qkv,
-                                                                   float* __restrict__ out, int H, float scale) {
-  __shared__ __attribute__((aligned(16))) __bf16 Kh[AL * KROW];
-  __shared__ __attribute__((aligned(16))) __bf16 Kl[AL * KROW];
-  __shared__ __attribute__((aligned(16))) __bf16 Vh[AD * VROW];
-  __shared__ __attribute__((aligned(16))) __bf16 Vl[AD * VROW];
-  __shared__ __attribute__((aligned(16))) __bf16 Ph[NWAVE][16 * 40];
-  __shared__ __attribute__((aligned(16))) __bf16 Pl[NWAVE][16 * 40];
-
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int HD = H * AD;
-  const int64_t rs = 3 * (int64_t)HD;             // qkv row stride
-  const float* base = qkv + (int64_t)b * AL * rs;
-
-  // stage K (row-major [key][d]) and V^T ([d][key]) as hi/lo bf16
-  for (int i = tid; i < AL * AD / 4; i += NWAVE * 64) {
-    const int key = i / (AD / 4), d4 = (i % (AD / 4)) * 4;
-    const float4 k4 = *reinterpret_cast<const float4*>(base + key * rs + HD + h * AD + d4);
-    const float4 v4 = *reinterpret_cast<const float4*>(base + key * rs + 2 * HD + h * AD + d4);
-    const float kv[4] = {k4.x, k4.y, k4.z, k4.w};
-    const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
-    bf16x4 khi, klo;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      __bf16 hi, lo;
-      split_bf16(kv[j], hi, lo);
-      khi[j] = hi; klo[j] = lo;
-      split_bf16(vv[j], hi, lo);
-      Vh[(d4 + j) * VROW + key] = hi; Vl[(d4 + j) * VROW + key] = lo;
-    }
-    *reinterpret_cast<bf16x4*>(Kh + key * KROW + d4) = khi;     // one 8-B LDS write per plane
-    *reinterpret_cast<bf16x4*>(Kl + key * KROW + d4) = klo;
-  }
-
-  // Q fragments straight from global: A[row = query][k = d]
-  const int fr = lane & 15, fg = lane >> 4;
-  const int q0 = wave * 16;
-  bf16x8 qh[2], ql[2];
-  {
-    const float* qr = base + (int64_t)(q0 + fr) * rs + h * AD;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const float4 a = *reinterpret_cast<const float4*>(qr + ks * 32 + fg * 8);
-      const float4 c = *reinterpret_cast<const float4*>(qr + ks * 32 + fg * 8 + 4);
-      const float v[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        __bf16 hi, lo;
-        split_bf16(v[j], hi, lo);
-        qh[ks][j] = hi; ql[ks][j] = lo;
-      }
-    }
-  }
-  __syncthreads();
-
-  // S = Q K^T : 12 key tiles of 16
-  f32x4 s[NWAVE];
-#pragma unroll
-  for (int t = 0; t < NWAVE; ++t) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int off = (t * 16 + fr) * KROW + ks * 32 + fg * 8;
-      const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Kh + off);
-      const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Kl + off);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ql[ks], kh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qh[ks], kl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qh[ks], kh, acc, 0, 0, 0);
-    }
-    s[t] = acc;
-  }
-  // softmax over keys, rows r: query q0 + 4*fg + r; a row's 192 values = 12 tiles x 16 lanes
-  float rmax[4], rsum[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float m = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < NWAVE; ++t) { s[t][r] *= scale; m = fmaxf(m, s[t][r]); }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    rmax[r] = m;
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < NWAVE; ++t) { const float e = exp_hw(s[t][r] - m); s[t][r] = e; sum += e; }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
-    rsum[r] = __builtin_amdgcn_rcpf(sum);     // P = e * (1 / sum): one rcp per row
-  }
-  (void)rmax;
-  // O = P V, P chunks of 32 keys (2 tiles) through the per-wave LDS slab
-  f32x4 o[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  __bf16* ph = Ph[wave];
-  __bf16* pl = Pl[wave];
-#pragma unroll
-  for (int c = 0; c < NWAVE / 2; ++c) {
-    // write P[16 q][32 keys] (normalised) as hi/lo, row stride 40 bf16
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float pv = s[2 * c + tt][r] * rsum[r];
-        __bf16 hi, lo;
-        split_bf16(pv, hi, lo);
-        const int off = (fg * 4 + r) * 40 + tt * 16 + fr;
-        ph[off] = hi; pl[off] = lo;
-      }
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): slab writes landed
-    __builtin_amdgcn_wave_barrier();
-    const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ph + fr * 40 + fg * 8);
-    const bf16x8 alo = *reinterpret_cast<const bf16x8*>(pl + fr * 40 + fg * 8);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int off = (j * 16 + fr) * VROW + c * 32 + fg * 8;
-      const bf16x8 vh = *reinterpret_cast<const bf16x8*>(Vh + off);
-      const bf16x8 vl = *reinterpret_cast<const bf16x8*>(Vl + off);
-      o[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, vh, o[j], 0, 0, 0);
-      o[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, vl, o[j], 0, 0, 0);
-      o[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, vh, o[j], 0, 0, 0);
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-  }
-  // out[b*L + q][h*D + d]
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = q0 + fg * 4 + r;
-      out[((int64_t)b * AL + q) * HD + h * AD + j * 16 + fr] = o[j][r];
-    }
-}
-
-// ----------------------------------------------------------------------------- v2
-// vit_attention_t_kernel — the same function computed transposed, in key chunks:
+// ----------------------------------------------------------------------------- v3
+// vit_attention_s_kernel — the function computed transposed, in key chunks of KC:
 //   S^T = K Q^T   (A = K rows from LDS, B = Q^T: the wave's queries, in registers)
 //   O^T = V^T P^T (A = V^T from LDS, B = P^T straight from the S^T accumulators)
 // The S^T accumulator of a 16-key tile gives lane (fr, fg) keys 4 fg + r of query fr, which is
@@ -173,207 +36,22 @@ __global__ __launch_bounds__(NWAVE * 64) void vit_attention_kernel(const float* 
 // Softmax runs over the rows of S^T (a query's keys: 4 r x 4 lane groups x tiles): two
 // shuffles per reduction. Keys are processed KC at a time with an online-softmax merge
 // (running max m, sum l, rescale of O by exp(m_old - m_new)), so only one chunk of K and V^T is
-// staged: 2 x (KC x 72 + 64 x (KC + 8)) bf16 = 36 KB at KC = 64 instead of 137 KB. A wave owns
-// QT 16-query tiles (each K / V^T fragment read from LDS feeds QT MFMAs); with QT = 2 a
-// workgroup is 6 waves and two or more workgroups share a CU, one staging while another
-// computes. 1 / l once per query at the end; O^T rows are d, so each lane stores 4
-// consecutive channels (16-B stores).
-template <int KC, int QT>
-__global__ __launch_bounds__(AL / 16 / QT * 64) __attribute__((amdgpu_waves_per_eu(QT == 2 ? 3 : 4))) void vit_attention_t_kernel(const float* __restrict__ qkv,
-                                                                           float* __restrict__ out, int H,
-                                                                           float scale) {
-  static_assert(AL % KC == 0 && KC % 32 == 0, "key chunk");
-  constexpr int NW = AL / 16 / QT;         // waves
-  constexpr int NT = NW * 64;
-  constexpr int KT = KC / 16;              // 16-key tiles per chunk
-  constexpr int VR = KC + 8;               // bf16 per V^T row (pad 16 B)
-  constexpr int KSZ = KC * KROW, VSZ = AD * VR;
-  __shared__ __attribute__((aligned(16))) __bf16 lds[2 * KSZ + 2 * VSZ];
-  __bf16* Kh = lds;
-  __bf16* Kl = lds + KSZ;
-  __bf16* Vh = lds + 2 * KSZ;
-  __bf16* Vl = lds + 2 * KSZ + VSZ;
+// staged: 2 x (KC x 80 + 64 x (KC + 8)) bf16 = 38 KB. 1 / l once per query at the end; O^T rows
+// are d, so each lane stores 4 consecutive channels (16-B stores).
+// It runs as a software pipeline over a STREAM of (head, key-chunk) items: a workgroup owns
+// `hpw` heads of one frame and walks their 192 / KC chunks each; the fp32 K / V (and, at a
+// head's first chunk, Q) of item i + 1 are loaded into registers while item i computes, and
+// written to LDS (split into planes) after the barrier that retires item i's reads. Only the
+// very first item's loads are exposed; the kernel reads q, k, v once and writes o once, so it is
+// bound by that HBM traffic (4 x 4 B x L x H x D per frame), not by the MFMAs.
+constexpr int KC = 64;         // key chunk (32 and 96 were A/B-ed in round 3, removed)
 
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int fr = lane & 15, fg = lane >> 4;
-  const int HD = H * AD;
-  const int64_t rs = 3 * (int64_t)HD;
-  const float* base = qkv + (int64_t)b * AL * rs;
-  const int q0 = wave * 16 * QT;
-
-  // Q^T B-fragments: lane (fr = query, fg) holds d = 32 ks + 8 fg .. + 7
-  bf16x8 qh[QT][2], ql[QT][2];
-#pragma unroll
-  for (int u = 0; u < QT; ++u) {
-    const float* qr = base + (int64_t)(q0 + u * 16 + fr) * rs + h * AD;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const float4 a = *reinterpret_cast<const float4*>(qr + ks * 32 + fg * 8);
-      const float4 c = *reinterpret_cast<const float4*>(qr + ks * 32 + fg * 8 + 4);
-      const float v[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        __bf16 hi, lo;
-        split_bf16(v[j], hi, lo);
-        qh[u][ks][j] = hi; ql[u][ks][j] = lo;
-      }
-    }
-  }
-
-  float m[QT], l[QT];                      // running max / sum of query fr of tile u
-  f32x4 o[QT][4];
-#pragma unroll
-  for (int u = 0; u < QT; ++u) {
-    m[u] = -1e30f; l[u] = 0.f;          // finite: exp_hw(-inf) would be NaN
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[u][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-
-  for (int c0 = 0; c0 < AL; c0 += KC) {
-    __builtin_amdgcn_sched_barrier(0);     // the previous chunk's reads stay above the barrier,
-    if (c0) __syncthreads();               // every wave done with the previous chunk
-    __builtin_amdgcn_sched_barrier(0);     // this chunk's below it
-    // K rows [key][d] as hi/lo: one float4 per item, 8-B LDS writes
-    for (int i = tid; i < KC * (AD / 4); i += NT) {
-      const int key = i / (AD / 4), d4 = (i % (AD / 4)) * 4;
-      const float4 k4 = *reinterpret_cast<const float4*>(base + (c0 + key) * rs + HD + h * AD + d4);
-      const float kv[4] = {k4.x, k4.y, k4.z, k4.w};
-      bf16x4 khi, klo;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        __bf16 hi, lo;
-        split_bf16(kv[j], hi, lo);
-        khi[j] = hi; klo[j] = lo;
-      }
-      *reinterpret_cast<bf16x4*>(Kh + key * KROW + d4) = khi;
-      *reinterpret_cast<bf16x4*>(Kl + key * KROW + d4) = klo;
-    }
-    // V^T [d][key]: an item is 4 keys x 4 channels (four float4 loads; 16 consecutive threads
-    // cover one key's 64 channels), transposed in registers, 8-B LDS writes of 4 keys
-    for (int i = tid; i < (KC / 4) * (AD / 4); i += NT) {
-      const int k4 = i / (AD / 4), d4 = (i % (AD / 4)) * 4;
-      float v[4][4];
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const float4 t = *reinterpret_cast<const float4*>(base + (c0 + k4 * 4 + kk) * rs + 2 * HD + h * AD + d4);
-        v[kk][0] = t.x; v[kk][1] = t.y; v[kk][2] = t.z; v[kk][3] = t.w;
-      }
-#pragma unroll
-      for (int dd = 0; dd < 4; ++dd) {
-        bf16x4 vhi, vlo;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-          __bf16 hi, lo;
-          split_bf16(v[kk][dd], hi, lo);
-          vhi[kk] = hi; vlo[kk] = lo;
-        }
-        *reinterpret_cast<bf16x4*>(Vh + (d4 + dd) * VR + k4 * 4) = vhi;
-        *reinterpret_cast<bf16x4*>(Vl + (d4 + dd) * VR + k4 * 4) = vlo;
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-    __builtin_amdgcn_sched_barrier(0);
-
-    // S^T tiles: rows = keys c0 + 16 t + 4 fg + r, column = query q0 + 16 u + fr
-    f32x4 s[QT][KT];
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {
-#pragma unroll
-      for (int u = 0; u < QT; ++u) s[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int off = (t * 16 + fr) * KROW + ks * 32 + fg * 8;
-        const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Kh + off);
-        const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Kl + off);
-#pragma unroll
-        for (int u = 0; u < QT; ++u) {
-          s[u][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl, qh[u][ks], s[u][t], 0, 0, 0);
-          s[u][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, ql[u][ks], s[u][t], 0, 0, 0);
-          s[u][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, qh[u][ks], s[u][t], 0, 0, 0);
-        }
-      }
-    }
-    // online softmax over this chunk's keys, per query
-#pragma unroll
-    for (int u = 0; u < QT; ++u) {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int t = 0; t < KT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { s[u][t][r] *= scale; mx = fmaxf(mx, s[u][t][r]); }
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mn = fmaxf(m[u], mx);
-      const float alpha = exp_hw(m[u] - mn);   // 0 on the first chunk (m = -1e30)
-      m[u] = mn;
-      float sum = 0.f;
-#pragma unroll
-      for (int t = 0; t < KT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { const float e = exp_hw(s[u][t][r] - mn); s[u][t][r] = e; sum += e; }
-      sum += __shfl_xor(sum, 16, 64);
-      sum += __shfl_xor(sum, 32, 64);
-      l[u] = l[u] * alpha + sum;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[u][j] *= alpha;
-    }
-
-    // O^T += V^T P^T, 32 keys per step
-#pragma unroll
-    for (int c = 0; c < KT / 2; ++c) {
-      bf16x8 ph[QT], pl[QT];
-#pragma unroll
-      for (int u = 0; u < QT; ++u)
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-          __bf16 hi, lo;
-          split_bf16(s[u][2 * c + (jj >> 2)][jj & 3], hi, lo);
-          ph[u][jj] = hi; pl[u][jj] = lo;
-        }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int off = (j * 16 + fr) * VR + c * 32 + fg * 4;
-        const bf16x4 h0 = *reinterpret_cast<const bf16x4*>(Vh + off);
-        const bf16x4 h1 = *reinterpret_cast<const bf16x4*>(Vh + off + 16);
-        const bf16x4 l0 = *reinterpret_cast<const bf16x4*>(Vl + off);
-        const bf16x4 l1 = *reinterpret_cast<const bf16x4*>(Vl + off + 16);
-        const bf16x8 vh = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        const bf16x8 vl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-#pragma unroll
-        for (int u = 0; u < QT; ++u) {
-          o[u][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vl, ph[u], o[u][j], 0, 0, 0);
-          o[u][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh, pl[u], o[u][j], 0, 0, 0);
-          o[u][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh, ph[u], o[u][j], 0, 0, 0);
-        }
-      }
-    }
-  }
-  // out[b*L + q][h*D + d], d = 16 j + 4 fg + r: one 16-B store per tile
-#pragma unroll
-  for (int u = 0; u < QT; ++u) {
-    const float inv = __builtin_amdgcn_rcpf(l[u]);
-    float* orow = out + ((int64_t)b * AL + q0 + u * 16 + fr) * HD + h * AD + fg * 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(orow + j * 16) = o[u][j] * inv;
-  }
-}
-
-// ----------------------------------------------------------------------------- v3
-// vit_attention_s_kernel — the transposed chunked kernel above (QT = 1, 12 waves) as a
-// software pipeline over a STREAM of (head, key-chunk) items: a workgroup owns `hpw` heads of
-// one frame and walks their 192 / KC chunks each; the fp32 K / V (and, at a head's first
-// chunk, Q) of item i + 1 are loaded into registers while item i computes, and written to LDS
-// (split into planes) after the barrier that retires item i's reads. Only the very first
-// item's loads are exposed; the kernel reads q, k, v once and writes o once, so it is bound by
-// that HBM traffic (4 x 4 B x L x H x D per frame), not by the MFMAs.
 // element strides of the q / k / v operand: frame, q->k->v, head, token (channel stride 1)
 struct AttnStrides {
   int64_t frame, which, head, tok;
 };
 
-template <int KC, bool OPL>
+template <bool OPL>
 __global__ __launch_bounds__(NWAVE * 64) void vit_attention_s_kernel(const float* __restrict__ qkv, AttnStrides sd,
                                                                     float* __restrict__ out, int H, int hpw,
                                                                     float scale) {
@@ -920,43 +598,20 @@ int attention_launch(const float* qkv, AttnStrides sd, float* out, int32_t B, in
   if (sd.frame < 0 || sd.which < 0 || sd.head < 0 || sd.tok < 0) return PRPE_EINVAL;
   const int64_t frame_extent = ((int64_t)(L - 1) * sd.tok + 2 * sd.which + (int64_t)(H - 1) * sd.head + D) * 4;
   const bool desc_ok = frame_extent < (1LL << 31);
-  // PRPE_ATTN selects the kernel for A/B runs: 1 = the round-1 kernel (P through LDS, all 192
-  // keys staged, 12 waves), KC*10 + QT = transposed kernel with KC-key chunks and QT query tiles
-  // per wave (322, 641, 642, 962); 32 / 64 / 96 = the streaming kernel with that chunk;
-  // 4 = the whole-head kernel (v4, round 5); default 4. The streaming and whole-head kernels take
-  // strided (e.g. head-major) operands.
-  static const int sel = [] {
-    const char* e = getenv("PRPE_ATTN");
-    return e ? atoi(e) : 4;
-  }();
-  const bool rowmajor = sd.frame == (int64_t)L * 3 * H * D && sd.which == (int64_t)H * D && sd.head == D &&
-                        sd.tok == (int64_t)3 * H * D;
-  const dim3 g(B * H);
   hipStream_t st = as_stream(stream);
   // streaming kernel: heads per workgroup = the largest divisor of H that still gives every CU
   // a workgroup (one 12-wave workgroup per CU at its register count)
   int hpw = H;
   while (hpw > 1 && ((int64_t)B * H / hpw < 256 || H % hpw)) --hpw;
   const dim3 gs(B * H / hpw);
+  if (out_planes && (uintptr_t)out % 32) return PRPE_EINVAL;
+  const dim3 blk(NWAVE * 64);
   if (out_planes) {
-    if ((uintptr_t)out % 32) return PRPE_EINVAL;
-    if (sel == 4 && desc_ok) hipLaunchKernelGGL((vit_attention_h_kernel<true>), gs, dim3(NWAVE * 64), 0, st, qkv, sd, out, H, hpw, scale);
-    else hipLaunchKernelGGL((vit_attention_s_kernel<64, true>), gs, dim3(NWAVE * 64), 0, st, qkv, sd, out, H, hpw, scale);
-    return launch_status();
-  }
-  if (sel == 4 && desc_ok) {
-    hipLaunchKernelGGL((vit_attention_h_kernel<false>), gs, dim3(NWAVE * 64), 0, st, qkv, sd, out, H, hpw, scale);
-    return launch_status();
-  }
-  switch (rowmajor ? sel : 64) {
-    case 1: hipLaunchKernelGGL(vit_attention_kernel, g, dim3(NWAVE * 64), 0, st, qkv, out, H, scale); break;
-    case 322: hipLaunchKernelGGL((vit_attention_t_kernel<32, 2>), g, dim3(6 * 64), 0, st, qkv, out, H, scale); break;
-    case 641: hipLaunchKernelGGL((vit_attention_t_kernel<64, 1>), g, dim3(12 * 64), 0, st, qkv, out, H, scale); break;
-    case 642: hipLaunchKernelGGL((vit_attention_t_kernel<64, 2>), g, dim3(6 * 64), 0, st, qkv, out, H, scale); break;
-    case 962: hipLaunchKernelGGL((vit_attention_t_kernel<96, 2>), g, dim3(6 * 64), 0, st, qkv, out, H, scale); break;
-    case 32: hipLaunchKernelGGL((vit_attention_s_kernel<32, false>), gs, dim3(NWAVE * 64), 0, st, qkv, sd, out, H, hpw, scale); break;
-    case 96: hipLaunchKernelGGL((vit_attention_s_kernel<96, false>), gs, dim3(NWAVE * 64), 0, st, qkv, sd, out, H, hpw, scale); break;
-    default: hipLaunchKernelGGL((vit_attention_s_kernel<64, false>), gs, dim3(NWAVE * 64), 0, st, qkv, sd, out, H, hpw, scale); break;
+    if (desc_ok) hipLaunchKernelGGL((vit_attention_h_kernel<true>), gs, blk, 0, st, qkv, sd, out, H, hpw, scale);
+    else hipLaunchKernelGGL((vit_attention_s_kernel<true>), gs, blk, 0, st, qkv, sd, out, H, hpw, scale);
+  } else {
+    if (desc_ok) hipLaunchKernelGGL((vit_attention_h_kernel<false>), gs, blk, 0, st, qkv, sd, out, H, hpw, scale);
+    else hipLaunchKernelGGL((vit_attention_s_kernel<false>), gs, blk, 0, st, qkv, sd, out, H, hpw, scale);
   }
   return launch_status();
 }

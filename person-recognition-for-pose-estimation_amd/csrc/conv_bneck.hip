@@ -67,9 +67,9 @@ constexpr int RING = 4;                                  // W1 / W2 ring stages 
 // LDS: TT (t1, then t2 in its first (MID/32) CHB2 bytes), then the W1 / W2 ring; a W3 part
 // overlays TT past t2 (and, at MID 64, ring stages 0-1). MID 64: 48 + 32 = 80 KB, two
 // workgroups per CU; MID 128: 96 + 64 = 160 KB, one.
-// TRT = output rows of the tile = waves of the workgroup (8: 8 x 16 pixels, 8 waves; 16 (MID 64
-// only, round 5): 16 x 16 pixels, 16 waves, one workgroup per CU -- every weight byte staged
-// into LDS serves twice the pixels, and the 3x3 halo is 1.27x the tile instead of 1.41x).
+// TRT = output rows of the tile = waves of the workgroup: 8 (8 x 16 pixels, 8 waves). The 16-row,
+// 16-wave tile of round 5 measured slower (profiles/r05_bneck_ablate.txt) and is kept as
+// tools/exp/bneck_16row.patch.
 template <int MIDT, bool PROJ, int TRT = 8> struct BShape {
   static constexpr int MID = MIDT, CIO = 4 * MIDT;
   static constexpr int TR = TRT, NW = TRT;
@@ -106,7 +106,7 @@ template <int MIDT, bool PROJ, int TRT = 8> struct BShape {
   static_assert(PPW >= 1 && STAGE == PPW * NW * PROWS * 64, "W ring pieces");
   static_assert(NKS3 * W3_STEP == W3_PART, "W3 part size");
   static_assert(NKS3 * 2 * (R3 / 16) == PW3 * NW && PW3 >= 1, "whole W3 pieces per wave and part");
-  static_assert(TR == 8 || (TR == 16 && MID == 64), "16-row tile: inner width 64 only (LDS)");
+  static_assert(TR == 8, "8-row tile");
   static_assert(W3_OFF + W3_PART <= RING_OFF + 2 * STAGE, "W3 part overlay below ring stage 2");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
@@ -647,21 +647,12 @@ __global__ __launch_bounds__(TRT * 64, (BShape<MIDT, PROJ, TRT>::WPC * TRT / 4))
 
 }  // namespace
 
-// tile rows: 8 (one workgroup of 8 waves per 8 x 16 tile, two per CU at inner width 64).
-// PRPE_BNECK_TR=16 selects the 16 x 16-pixel, 16-wave tile for the inner-width-64 blocks (A/B
-// runs, round 5): it halves the weight bytes staged per pixel and the halo (1.41x -> 1.27x) but
-// measured slower -- layer1 identity block 5.21 -> 5.80 ms, projection 4.05 -> 4.38 ms at bs = 256
-// (profiles/r05_bneck_ablate.txt): one 16-wave workgroup per CU stalls every wave at each
-// barrier where two 8-wave workgroups cover each other's, and phase 1's 21 haloed row blocks
-// leave 11 of 16 waves idle for half the phase
-int bneck_rows(int mid) {
-  static const int tr = [] {
-    const char* e = getenv("PRPE_BNECK_TR");
-    return e && e[0] == '1' && e[1] == '6' ? 16 : 8;
-  }();
-  return mid == 64 ? tr : 8;
-}
-
+// tile rows: 8 (one workgroup of 8 waves per 8 x 16 tile, two per CU at inner width 64). The
+// 16 x 16-pixel, 16-wave tile for the inner-width-64 blocks (round 5) halves the weight bytes
+// staged per pixel and the halo (1.41x -> 1.27x) but measured slower -- layer1 identity block
+// 5.21 -> 5.80 ms, projection 4.05 -> 4.38 ms at bs = 256 (profiles/r05_bneck_ablate.txt): one
+// 16-wave workgroup per CU stalls every wave at each barrier where two 8-wave workgroups cover
+// each other's, and phase 1's 21 haloed row blocks leave 11 of 16 waves idle for half the phase
 template <int MIDT, bool PROJ, int TRT>
 int bneck_launch_t(BneckK kp, hipStream_t st) {
   kp.tiles_w = (kp.W + TC - 1) / TC;
@@ -673,10 +664,7 @@ int bneck_launch_t(BneckK kp, hipStream_t st) {
   return launch_status();
 }
 
-int bneck_launch(const BneckK& kp, int rows, hipStream_t st) {
-  if (rows == 16 && kp.mid == 64)
-    return kp.proj ? bneck_launch_t<64, true, 16>(kp, st) : bneck_launch_t<64, false, 16>(kp, st);
-  if (rows != 8) return PRPE_EINVAL;
+int bneck_launch(const BneckK& kp, hipStream_t st) {
   if (kp.proj) return bneck_launch_t<64, true, 8>(kp, st);
   return kp.mid == 64 ? bneck_launch_t<64, false, 8>(kp, st) : bneck_launch_t<128, false, 8>(kp, st);
 }
@@ -716,5 +704,5 @@ extern "C" int prpe_bottleneck(const prpe_bneck_desc* d, void* stream) {
     kp.wh[l] = d->w_h16[l]; kp.wl[l] = d->w_l16[l]; kp.kp[l] = d->k_pad[l];
     kp.sc[l] = d->scale16[l]; kp.bi[l] = d->bias[l];
   }
-  return bneck_launch(kp, bneck_rows(MID), as_stream(stream));
+  return bneck_launch(kp, as_stream(stream));
 }

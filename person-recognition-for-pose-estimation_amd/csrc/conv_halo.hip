@@ -508,30 +508,20 @@ int launch_halo_kind(const ConvK& kp, int prec, hipStream_t st) {
                      : launch_halo<NW, TR, TC, TN, false, false, 0, WN>(kp, st);
 }
 
-// epilogue tap GEMM: the 8 x 16-pixel, 128-column tile (NW = 4) or the 16 x 16 one (NW = 8)
-template <int TAPS, int WN, int NW = 4>
-int launch_halo_taps_t(const ConvK& kp, int prec, hipStream_t st) {
+// epilogue tap GEMM: the 8 x 16-pixel, 128-column tile (NW = 4) or the 16 x 16 one (NW = 8).
+// (The 2 x 2 wave grid was A/B-ed for these and for the automatic tile in round 2: in the model at
+// bs = 256 ViT adapter.7 +0.6 %, face-YOLO .10 +2.8 % (two block barriers per row block in the
+// chain epilogue), AdaFace .7 -2.8 %, bench 1363 -> 1357 frames/s
+// (profiles/r02_layer_profile_halo_wn.txt), although the micro-bench on random data had it 4-12 %
+// faster (profiles/r02_conv_bench_halo_wn.txt); kept as tools/exp/halo_taps_wn2.patch. Tiles
+// 36 / 37 still force it for a plain conv.)
+template <int TAPS, int NW>
+int launch_halo_taps(const ConvK& kp, int prec, hipStream_t st) {
   constexpr int TR = NW == 4 ? 8 : 16;
   if (prec == 4) return PRPE_EINVAL;
-  if (prec == 3) return launch_halo<NW, TR, 16, 8, true, false, TAPS, WN>(kp, st);
-  return kp.x_planes ? launch_halo<NW, TR, 16, 8, false, true, TAPS, WN>(kp, st)
-                     : launch_halo<NW, TR, 16, 8, false, false, TAPS, WN>(kp, st);
-}
-// PRPE_HALO_WN=2: the 2 x 2 wave grid (WN = 2) for the automatic and epilogue-GEMM tiles.
-// Off by default: in the model at bs = 256 it measured ViT adapter.7 +0.6 %, face-YOLO .10
-// +2.8 % (two block barriers per row block in the chain epilogue), AdaFace .7 -2.8 %, bench
-// 1363 -> 1357 frames/s (profiles/r02_layer_profile_halo_wn.txt), although the micro-bench on
-// random data had it 4-12 % faster (profiles/r02_conv_bench_halo_wn.txt).
-int halo_wn() {
-  static const int wn = [] {
-    const char* e = getenv("PRPE_HALO_WN");
-    return e && e[0] == '2' ? 2 : 1;
-  }();
-  return wn;
-}
-int launch_halo_taps(const ConvK& kp, int prec, hipStream_t st) {
-  if (halo_wn() == 2) return kp.w3 ? launch_halo_taps_t<2, 2>(kp, prec, st) : launch_halo_taps_t<1, 2>(kp, prec, st);
-  return kp.w3 ? launch_halo_taps_t<2, 1>(kp, prec, st) : launch_halo_taps_t<1, 1>(kp, prec, st);
+  if (prec == 3) return launch_halo<NW, TR, 16, 8, true, false, TAPS>(kp, st);
+  return kp.x_planes ? launch_halo<NW, TR, 16, 8, false, true, TAPS>(kp, st)
+                     : launch_halo<NW, TR, 16, 8, false, false, TAPS>(kp, st);
 }
 
 }  // namespace
@@ -563,13 +553,8 @@ bool conv_halo_eligible(const ConvK& kp, int prec, int km, int tile) {
 // much) takes it from 14 x 14 up whatever the waste: the IR-50 body's 14x14 256->256 -38 %,
 // 28x28 128->128 -21 %, 56x56 64->64 -30 % at bs = 256 (profiles/r04_conv_bench_ir50_halo.txt);
 // 7 x 7 stays on the wave kernel (one 8 x 16 tile per frame, 2.6x waste: no gain).
-// (PRPE_P4_HALO=0 in the environment restores the waste rule for precision 4: A/B runs)
 bool conv_halo_auto(const ConvK& kp, int prec) {
-  static const bool p4_halo = [] {
-    const char* e = getenv("PRPE_P4_HALO");
-    return !(e && e[0] == '0');
-  }();
-  if (prec == 4 && p4_halo && kp.Ho >= 14 && kp.Wo >= 14) return true;
+  if (prec == 4 && kp.Ho >= 14 && kp.Wo >= 14) return true;
   if (prec == 0 && !kp.x_planes) return false;
   const int tc = 16, tr = 8;
   const int64_t covered = (int64_t)((kp.Ho + tr - 1) / tr) * tr * ((kp.Wo + tc - 1) / tc) * tc;
@@ -578,23 +563,16 @@ bool conv_halo_auto(const ConvK& kp, int prec) {
 
 // tile 30 = auto: 8 x 16 output pixels, 4 waves (two workgroups per CU), 128 output channels
 // per workgroup, or 64 when Co <= 64 (tools/conv_bench.py, profiles/r02_conv_bench_halo.txt);
-// 31..35 force a configuration
+// 31..37 force a configuration
 int conv_halo_launch(const ConvK& kp, int prec, int tile, hipStream_t st) {
-  // PRPE_HALO_TILE=32 / 33 makes that tile the automatic choice for Co > 64 (A/B runs; for the
-  // epilogue-GEMM convs 32 selects the 16 x 16-pixel 8-wave form)
-  static const int env_tile = [] {
-    const char* e = getenv("PRPE_HALO_TILE");
-    const int t = e ? atoi(e) : 0;
-    return t == 32 || t == 33 ? t : 0;
-  }();
-  if (tile == 30 && env_tile && kp.Co > 64 && (!kp.w2 || env_tile == 32)) tile = env_tile;
-  if (kp.w2) {
-    if (tile == 32) return kp.w3 ? launch_halo_taps_t<2, 1, 8>(kp, prec, st) : launch_halo_taps_t<1, 1, 8>(kp, prec, st);
-    return tile == 30 || tile == 31 ? launch_halo_taps(kp, prec, st) : PRPE_EINVAL;
+  if (kp.w2) {                                              // epilogue GEMM: 32 = the 16 x 16-pixel 8-wave form
+    if (tile == 32) return kp.w3 ? launch_halo_taps<2, 8>(kp, prec, st) : launch_halo_taps<1, 8>(kp, prec, st);
+    if (tile != 30 && tile != 31) return PRPE_EINVAL;
+    return kp.w3 ? launch_halo_taps<2, 4>(kp, prec, st) : launch_halo_taps<1, 4>(kp, prec, st);
   }
   // precision 4 takes the 2 x 2 wave grid for Co > 64 (half the B fragment reads per wave; AdaFace
   // adapter.7 3.05 -> 2.78 ms in the model at bs = 256, profiles/r04_layer_profile_halo_p4_wn2.txt)
-  if (tile == 30) tile = kp.Co <= 64 ? 34 : (halo_wn() == 2 || prec == 4 ? 36 : 31);
+  if (tile == 30) tile = kp.Co <= 64 ? 34 : (prec == 4 ? 36 : 31);
   switch (tile) {
     case 31: return launch_halo_kind<4, 8, 16, 8>(kp, prec, st);     // 8 x 16 px, 4 waves, 128 ch
     case 32: return launch_halo_kind<8, 16, 16, 8>(kp, prec, st);    // 16 x 16 px, 8 waves, 128 ch

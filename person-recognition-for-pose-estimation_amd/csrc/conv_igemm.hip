@@ -28,7 +28,6 @@
 // Reference arithmetic replaced: torch Conv2d (+BatchNorm2d eval +act +residual) at every
 // call site listed in include/prpe.h (prpe_conv2d).
 #include "conv.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -730,64 +729,37 @@ extern "C" int prpe_conv2d(const prpe_conv_desc* d, void* stream) {
   // direct global->LDS kernel (conv_glds.hip) for chunked inputs with Co > 32: tiles 10..12 only
   // (never the automatic choice since round 1: this file's 256x64 tile measures 27 % faster on
   // its shapes in isolation, profiles/r01_conv_bench_sweep_v4.txt, and -0.6..1.0 ms per
-  // sequential forward; the round-1 environment switch back to it was removed in round 6)
-  static const int wave_on = [] {
-    const char* e = getenv("PRPE_CONV_WAVE");
-    return e && e[0] == '0' ? 0 : 1;
-  }();
-  // haloed-tile 3x3 kernel (conv_halo.hip): the automatic choice for the 3x3 / s1 / p1 convs
-  // where conv_halo_auto says it wins (profiles/r02_conv_bench_halo.txt, in-model per-layer
-  // profile r02_layer_profile_halo.txt); tiles 30..35 force it, PRPE_CONV_HALO=0 turns it off
-  static const int halo_on = [] {
-    const char* e = getenv("PRPE_CONV_HALO");
-    return e && e[0] == '0' ? 0 : 1;
-  }();
+  // sequential forward).
+  // The automatic routes below each had an on / off switch in the environment for their A/B runs
+  // (removed in rounds 6 and 7); prpe_conv_desc.tile forces a kernel and tile per call.
+  if (tile >= 40 && tile < 50) return conv_gemm_eligible(kp, prec) ? conv_gemm_launch(kp, prec, tile, st) : PRPE_EINVAL;
   // 256-row GEMM kernel (conv_gemm.hip): the automatic choice for eligible 1x1 convs / linears
   // over at least 32K pixels whose input is in the planes format (in the model: ViT fc2 -16 %,
   // YOLO adapter 1x1 -9 %; with fp32 input it measured no better than the wave kernel there,
-  // profiles/r02_layer_profile_gemm_ab.txt); tiles 40..42 force it, PRPE_CONV_GEMM=0 turns it off
-  static const int gemm_on = [] {
-    const char* e = getenv("PRPE_CONV_GEMM");
-    return e && e[0] == '0' ? 0 : 1;
-  }();
-  if (tile >= 40 && tile < 50) return conv_gemm_eligible(kp, prec) ? conv_gemm_launch(kp, prec, tile, st) : PRPE_EINVAL;
-  // precision 3 (the trunk's fp32 activations, split per frame) on the GEMM kernel: off by
-  // default. PRPE_CONV_GEMM_P3=auto routes the deep 1x1s without a residual (K >= 1024), which
-  // measured 10-13 % faster than the wave kernel's 256x128 tile while that tile was held to one
-  // workgroup per CU by its 132-VGPR build (profiles/r05_layer_profile_p3gemm.txt); with the tile
-  // back at 128 VGPRs the wave kernel is the faster one again (profiles/r05_p3gemm_recheck.txt).
-  // =1 routes every eligible precision-3 conv (A/B runs).
-  static const int gemm_p3 = [] {
-    const char* e = getenv("PRPE_CONV_GEMM_P3");
-    return e && e[0] == '1' ? 1 : e && e[0] == 'a' ? 2 : 0;
-  }();
-  const bool p3_gemm = prec == 3 && (gemm_p3 == 1 || (gemm_p3 == 2 && kp.K >= 1024 && kp.res_mode == PRPE_RES_NONE));
-  // PRPE_GEMM_TILE=41..49 overrides the automatic GEMM tile (A/B runs)
-  static const int gemm_tile = [] {
-    const char* e = getenv("PRPE_GEMM_TILE");
-    const int t = e ? atoi(e) : 40;
-    return t >= 41 && t <= 49 ? t : 40;
-  }();
-  // the 256 x 256 tile (41) for the GEMMs that write the planes format through an activation
-  // (ViT fc1: GELU, face-YOLO adapter.7: SiLU), the 256 x 128 one (40) for the rest: measured in
-  // the model at bs = 256 (profiles/r05_layer_profile_gemm_tiles.txt): fc1 0.783 -> 0.725 ms,
+  // profiles/r02_layer_profile_gemm_ab.txt); tiles 40..49 force it.
+  // Precision 3 (the trunk's fp32 activations, split per frame) is never routed to it: the deep
+  // 1x1s without a residual (K >= 1024) measured 10-13 % faster there than on the wave kernel's
+  // 256x128 tile while that tile was held to one workgroup per CU by its 132-VGPR build
+  // (profiles/r05_layer_profile_p3gemm.txt); with the tile back at 128 VGPRs the wave kernel is
+  // the faster one again (profiles/r05_p3gemm_recheck.txt).
+  // The 256 x 256 tile for the GEMMs that write the planes format through an activation (ViT
+  // fc1: GELU, face-YOLO adapter.7: SiLU), the 256 x 128 one (40) for the rest: measured in the
+  // model at bs = 256 (profiles/r05_layer_profile_gemm_tiles.txt): fc1 0.783 -> 0.725 ms,
   // adapter.7 6.71 -> 6.33 ms on 41, while fc2 / proj (residual epilogues) and qkv lose on it
-  // (0.636 -> 0.729, 0.220 -> 0.264, 0.526 -> 0.542). PRPE_GEMM_WIDE=0 keeps 40 everywhere (A/B).
+  // (0.636 -> 0.729, 0.220 -> 0.264, 0.526 -> 0.542).
   // The wide tile runs persistent (47: each workgroup walks tiles, the next tile's first K-step
   // DMA'd under this tile's epilogue): fc1 8.77 -> 8.39 ms over the 12 layers, face-YOLO adapter.7
-  // 6.29 -> 5.94 ms (profiles/r05_gemm_persist.txt); PRPE_GEMM_WIDE=1 keeps the plain 41.
-  static const int gemm_wide = [] {
-    const char* e = getenv("PRPE_GEMM_WIDE");
-    return e && e[0] == '0' ? 0 : e && e[0] == '1' ? 1 : 2;
-  }();
-  if (tile == 0 && gemm_on && (kp.x_planes || p3_gemm) && kp.M >= (1 << 15) &&
-      conv_gemm_eligible(kp, prec)) {
-    const bool wide = gemm_wide && gemm_tile == 40 && kp.y_planes && kp.act != PRPE_ACT_NONE && kp.Co % 256 == 0;
-    return conv_gemm_launch(kp, prec, wide ? (gemm_wide == 2 ? 47 : 41) : gemm_tile, st);
+  // 6.29 -> 5.94 ms against the plain 41 (profiles/r05_gemm_persist.txt).
+  if (tile == 0 && kp.x_planes && kp.M >= (1 << 15) && conv_gemm_eligible(kp, prec)) {
+    const bool wide = kp.y_planes && kp.act != PRPE_ACT_NONE && kp.Co % 256 == 0;
+    return conv_gemm_launch(kp, prec, wide ? 47 : 40, st);
   }
+  // haloed-tile 3x3 kernel (conv_halo.hip): the automatic choice for the 3x3 / s1 / p1 convs
+  // where conv_halo_auto says it wins (profiles/r02_conv_bench_halo.txt, in-model per-layer
+  // profile r02_layer_profile_halo.txt); tiles 30..37 force it
   if (tile >= 30 && tile < 40)
     return conv_halo_eligible(kp, prec, km, tile) ? conv_halo_launch(kp, prec, tile, st) : PRPE_EINVAL;
-  if (tile == 0 && halo_on && conv_halo_auto(kp, prec) && conv_halo_eligible(kp, prec, km))
+  if (tile == 0 && conv_halo_auto(kp, prec) && conv_halo_eligible(kp, prec, km))
     return conv_halo_launch(kp, prec, 30, st);
   // precision 3 (split fp16) and 4 (one fp16 plane) are implemented by the wave-row kernel only
   if (prec >= 3) {
@@ -799,7 +771,7 @@ extern "C" int prpe_conv2d(const prpe_conv_desc* d, void* stream) {
   if (tile >= 10) return conv_glds_eligible(kp, prec, km) ? conv_glds_launch(kp, prec, tile, st) : PRPE_EINVAL;
   // wave-row kernel everywhere it applies except two-plane Co <= 64, where the register-staged
   // 256x64 tile measured faster (profiles/r01_conv_bench_wave.txt, r01_conv_bench_sweep_v4.txt)
-  if (tile == 0 && wave_on && y.c > 32 && (prec == 2 || y.c > 64) && conv_wave_eligible(kp, prec, km))
+  if (tile == 0 && y.c > 32 && (prec == 2 || y.c > 64) && conv_wave_eligible(kp, prec, km))
     return conv_wave_launch(kp, prec, 20, st);
   // measured (tools/conv_bench.py, profiles/r01_conv_bench_tiles.txt): the 3-plane mode wants the
   // 256x128 8-wave tile for wide Co (operand traffic per MFMA halves; +30%), 128x64 below;

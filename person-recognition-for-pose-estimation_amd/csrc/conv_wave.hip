@@ -30,7 +30,6 @@
 // Epilogue: each wave stages its accumulator rows through a private 16-row LDS slice and
 // writes whole-row 16-B vectors (scale/bias, act, residual), no block barrier.
 #include "conv.h"
-#include <stdlib.h>
 
 namespace prpe_k {
 namespace {
@@ -673,36 +672,20 @@ int conv_wave_launch(const ConvK& kp, int prec, int tile, hipStream_t st) {
     // the A operand's one-K-step register lookahead then meets its L2 latency: adapters' 3x3
     // -8..10 %, YOLO adapter 1x1 -12 %, ViT fc1 -4 % in isolation, +0.2..0.4 % on the
     // concurrent-heads bench), short-K or narrow precision-3 convs the 256x64 tile
-    // PRPE_WAVE_WIDE=<tile> in the environment overrides the wide-shape choice (A/B runs)
-    static const int wide = [] {
-      const char* e = getenv("PRPE_WAVE_WIDE");
-      return e ? atoi(e) : 28;
-    }();
     // precision 3: Co <= 64 on the 256 x 64 tile (25); Co > 64 on the wide tile at any K: the
     // short-K residual GEMMs of the trunk (conv3 + residual, K = 64 / 128 / dual 128) run 16-19 %
     // faster on it than on the 256 x 64 tile at bs = 256 (profiles/r01_conv_bench_sweep_v4.txt;
-    // bench +1.2 %). (The round-1/2 A/B switches of both choices were removed in round 6.)
+    // bench +1.2 %).
     // precision 3, Co > 64: the 256 x 128 8-wave tile (wave 32 x 128, 3-stage ring) since round 4:
     // trunk convs 68.6 -> 66.1 ms at bs = 256 against the 128 x 128 2-stage tile, every unfused
     // trunk conv faster (profiles/r04_layer_profile_trunk_wide3_sweep.txt; round 2 had measured the
-    // opposite, before the buffer-descriptor addressing of round 3)
-    static const int wide3 = [] {
-      const char* e = getenv("PRPE_WAVE_WIDE3");
-      return e ? atoi(e) : 23;
-    }();
-    // PRPE_WAVE_P4=<26|27> overrides the precision-4 choice for Co > 64 (A/B runs)
-    static const int wide4 = [] {
-      const char* e = getenv("PRPE_WAVE_P4");
-      return e && atoi(e) == 26 ? 26 : 27;
-    }();
-    static const int tile2 = [] {
-      const char* e = getenv("PRPE_WAVE_P2");
-      return e ? atoi(e) : 27;
-    }();
-    if (prec == 0) tile = wide;
-    else if (prec == 3) tile = kp.Co > 64 ? wide3 : 25;
-    else if (prec == 4) tile = kp.Co > 64 ? wide4 : 25;  // (the precision-3 overrides do not apply)
-    else tile = kp.Co > 64 && kp.K > 128 ? tile2 : 24;
+    // opposite, before the buffer-descriptor addressing of round 3).
+    // (Every choice here had an A/B switch in the environment; removed in rounds 6 and 7: force
+    // a tile per call through prpe_conv_desc.tile instead.)
+    if (prec == 0) tile = 28;
+    else if (prec == 3) tile = kp.Co > 64 ? 23 : 25;
+    else if (prec == 4) tile = kp.Co > 64 ? 27 : 25;
+    else tile = kp.Co > 64 && kp.K > 128 ? 27 : 24;
   }
   if (prec == 0) {
     switch (tile) {

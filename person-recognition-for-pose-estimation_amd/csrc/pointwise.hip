@@ -9,7 +9,6 @@
 //   l2norm        : row L2 normalisation
 //   dfl_decode    : YOLO head eval decode (DFL softmax-expectation, anchors, strides, sigmoid)
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -122,9 +121,8 @@ __device__ __forceinline__ void up_hrow(const float* __restrict__ zrow, const Up
 
 // ACT >= 0: the epilogue activation as a compile-time constant (one activation's code and
 // registers per instantiation); -1 reads p.act
-// ABL (diagnostic builds, PRPE_UPCONV_ABL): 1 = no z loads (H rows from registers), 2 = no y
-// stores (kept live through a never-true condition), 3 = both
-template <int VW, int ACT, int ABL = 0>
+// (the "no z loads" / "no y stores" ablations of round 4: tools/exp/upconv_ablate.patch)
+template <int VW, int ACT>
 __global__ __launch_bounds__(256) void upconv_fused_kernel(UpK p, int R, int rblocks) {
   // XCD-aware order (p.xcd): consecutive chunks share their z source columns, so each XCD
   // takes a contiguous range of the logical blocks instead of every 8th one
@@ -197,21 +195,13 @@ __global__ __launch_bounds__(256) void upconv_fused_kernel(UpK p, int R, int rbl
       const int y1 = y0 < Hi - 1 ? y0 + 1 : y0;
       if (y0 != cur[dy]) {
         const float* zt = zn + dy * tap_row;
-        if constexpr ((ABL & 1) != 0) {
+        if (y0 == cur[dy] + 1) {
 #pragma unroll
-          for (int v = 0; v < VW; ++v) {
-            hA[dy][v] = hB[dy][v];
-            hB[dy][v] = ux[v % 3].l1 * (float)(y1 + v);
-          }
+          for (int v = 0; v < VW; ++v) hA[dy][v] = hB[dy][v];
         } else {
-          if (y0 == cur[dy] + 1) {
-#pragma unroll
-            for (int v = 0; v < VW; ++v) hA[dy][v] = hB[dy][v];
-          } else {
-            up_hrow<VW>(zt + (int64_t)y0 * p.z.sh, ux, xvalid, hA[dy], zsc);
-          }
-          up_hrow<VW>(zt + (int64_t)y1 * p.z.sh, ux, xvalid, hB[dy], zsc);
+          up_hrow<VW>(zt + (int64_t)y0 * p.z.sh, ux, xvalid, hA[dy], zsc);
         }
+        up_hrow<VW>(zt + (int64_t)y1 * p.z.sh, ux, xvalid, hB[dy], zsc);
         cur[dy] = y0;
       }
 #pragma unroll
@@ -232,10 +222,6 @@ __global__ __launch_bounds__(256) void upconv_fused_kernel(UpK p, int R, int rbl
 #pragma unroll
     for (int v = 0; v < VW; ++v) ym = fmaxf(ym, fabsf(out[v]));
     float* y = yn + (int64_t)oy * p.y.sh + yo;
-    if constexpr ((ABL & 2) != 0) {
-      if (out[0] + out[VW - 1] == 12345.678f) y[0] = out[0];
-      continue;
-    }
     // non-temporal stores: the output is not re-read here, and z's lines stay in L2
     // (-6 % on the adapters' shapes, tools/upconv_bench.py)
     if constexpr (VW == 4) {
@@ -1158,13 +1144,8 @@ extern "C" int prpe_upconv3x3(const prpe_view* z, const prpe_view* y, int32_t al
   }
   // LDS-DMA path (upconv_dma_kernel): 4-channel vectors, Co % 32 == 0, channel-contiguous y,
   // every output column tile's source window <= UPD_NSC columns, every source interval >= 5
-  // output rows (the kernel's vmcnt counting), one frame of z < 2^31 bytes. PRPE_UPCONV_DMA=0
-  // keeps the fused kernel (A/B runs).
-  static const int dma_env = [] {
-    const char* e = getenv("PRPE_UPCONV_DMA");
-    return e ? atoi(e) : 1;
-  }();
-  if (dma_env && v4 && y->c % UPD_C == 0 && y->sc == 1 && z->sc == 1 && y->h <= UP_MAX_R && upd_geometry_ok(z, y, p.ac)) {
+  // output rows (the kernel's vmcnt counting), one frame of z < 2^31 bytes
+  if (v4 && y->c % UPD_C == 0 && y->sc == 1 && z->sc == 1 && y->h <= UP_MAX_R && upd_geometry_ok(z, y, p.ac)) {
     const int R = y->h, rblocks = 1;
     const int ctiles = (y->w + UPD_W - 1) / UPD_W, cblocks = y->c / UPD_C;
     const int64_t nb = (int64_t)y->n * rblocks * ctiles * cblocks;
@@ -1184,13 +1165,8 @@ extern "C" int prpe_upconv3x3(const prpe_view* z, const prpe_view* y, int32_t al
   }
   // fused path: R output rows per thread; shrink R while the grid would not fill the chip
   // rows per thread: each thread's first rows rebuild both interpolation rows of every dy, so
-  // long runs amortise that (measured, tools/upconv_bench.py bs=256: R 32 -> 256 = +4..10 %);
-  // PRPE_UPCONV_R overrides it for A/B runs
-  static const int r_env = [] {
-    const char* e = getenv("PRPE_UPCONV_R");
-    return e ? atoi(e) : 256;
-  }();
-  int R = r_env < UP_MAX_R ? (r_env > 0 ? r_env : 1) : UP_MAX_R;
+  // long runs amortise that (measured, tools/upconv_bench.py bs=256: R 32 -> 256 = +4..10 %)
+  int R = UP_MAX_R < 256 ? UP_MAX_R : 256;
   while (R > 4 && (int64_t)y->n * ((y->h + R - 1) / R) * p.chunks < 8192) R /= 2;
   const int rblocks = (y->h + R - 1) / R;
   const int64_t nb = (int64_t)y->n * rblocks * p.chunks;
@@ -1204,23 +1180,6 @@ extern "C" int prpe_upconv3x3(const prpe_view* z, const prpe_view* y, int32_t al
     return PRPE_EINVAL;
   p.xcd = 1;   // XCD-contiguous block order (round 2: -12..27 % per launch; its A/B switch removed in round 6)
   const dim3 g((unsigned)nb);
-  static const int abl = [] {
-    const char* e = getenv("PRPE_UPCONV_ABL");
-    return e ? atoi(e) : 0;
-  }();
-#define PRPE_UP_ABL(A)                                                                                     \
-  if (abl == 1) hipLaunchKernelGGL((upconv_fused_kernel<4, A, 1>), g, dim3(256), 0, st, p, R, rblocks);     \
-  else if (abl == 2) hipLaunchKernelGGL((upconv_fused_kernel<4, A, 2>), g, dim3(256), 0, st, p, R, rblocks); \
-  else hipLaunchKernelGGL((upconv_fused_kernel<4, A, 3>), g, dim3(256), 0, st, p, R, rblocks);
-  if (abl && v4 && act == PRPE_ACT_SILU) {
-    PRPE_UP_ABL(PRPE_ACT_SILU)
-    return launch_status();
-  }
-  if (abl && v4 && act == PRPE_ACT_GELU) {
-    PRPE_UP_ABL(PRPE_ACT_GELU)
-    return launch_status();
-  }
-#undef PRPE_UP_ABL
   if (!v4) hipLaunchKernelGGL((upconv_fused_kernel<1, -1>), g, dim3(256), 0, st, p, R, rblocks);
   else if (act == PRPE_ACT_NONE) hipLaunchKernelGGL((upconv_fused_kernel<4, PRPE_ACT_NONE>), g, dim3(256), 0, st, p, R, rblocks);
   else if (act == PRPE_ACT_SILU) hipLaunchKernelGGL((upconv_fused_kernel<4, PRPE_ACT_SILU>), g, dim3(256), 0, st, p, R, rblocks);

@@ -142,15 +142,34 @@ class Engine:
     def empty(self, *shape):
         return torch.empty(*shape, device=self.device, dtype=torch.float32)
 
-    def bordered(self, B, H, W, C):
-        """A [B, H+2, W+2, C] buffer whose one-pixel border is zero (allocated zeroed once per
-        shape; only its interior is ever written): the input of an unpadded 3x3 conv."""
-        key = ("bordered", B, H, W, C)
+    def _batch_buf(self, kind, B, shape):
+        """The zeroed scratch buffer [B, *shape] of ``kind``, allocated once per shape (callers
+        only ever write its interior, so its border stays zero). A new batch size drops the
+        kind's buffers of every other batch size: one batch size at a time."""
+        key = (kind, B, *shape)
         t = self._aux.get(key)
         if t is None:
-            t = torch.zeros(B, H + 2, W + 2, C, device=self.device, dtype=torch.float32)
+            for k in [k for k in self._aux if isinstance(k, tuple) and k[0] == kind and k[1] != B]:
+                del self._aux[k]
+            t = torch.zeros(B, *shape, device=self.device, dtype=torch.float32)
             self._aux[key] = t
         return t
+
+    def bordered(self, B, H, W, C):
+        """A [B, H+2, W+2, C] buffer whose one-pixel border is zero: the input of an unpadded
+        3x3 conv."""
+        return self._batch_buf("bordered", B, (H + 2, W + 2, C))
+
+    def _timed(self, watch, events, key, rec, launch):
+        """Run ``launch()``; when ``watch`` is in ``self.watch``, between two HIP events, and
+        append (e0, e1, *rec) to ``events[key]`` (bench roofline, tools/layer_profile.py)."""
+        if watch not in self.watch:
+            return launch()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+        events.setdefault(key, []).append((e0, e1, *rec))
 
     def dev(self, key, fn=None):
         t = self._aux.get(key)
@@ -277,14 +296,8 @@ class Engine:
         kw = dict(res=res, res_mode=res_mode, act=act, precision=prec, tile=p.tile, x_amax=xa, y_amax=ya, x2=x2,
                   x2_amax=x2_amax if prec == 3 else None, x_planes=x_planes, y_planes=y_planes, w2=w2, y2=y2,
                   **stage2)
-        if p.name in self.watch:          # HIP events around one kernel (bench roofline)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            ops.conv2d(x, p, out, **kw)
-            e1.record()
-            self.events.setdefault(p.name, []).append((e0, e1, B * Ho * Wo, p, prec, x.numel()))
-        else:
-            ops.conv2d(x, p, out, **kw)
+        self._timed(p.name, self.events, p.name, (B * Ho * Wo, p, prec, x.numel()),
+                    lambda: ops.conv2d(x, p, out, **kw))
         out._prpe_amax = ya
         if y_planes:
             out._prpe_planes = True
@@ -320,14 +333,8 @@ class Engine:
         # a precision-3/4 consumer reads the output's per-frame max|y| as its activation scale
         ya = self.amax_slot(B) if self.precision in F16_PRECS else None
         args = (z, out, align_corners, self._aux[key], self._aux[key + "b"], slope, act)
-        if name + ":upconv" in self.watch:     # HIP events around the launch (tools/layer_profile.py)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            ops.upconv3x3(*args, y_planes=planes, y_amax=ya)
-            e1.record()
-            self.up_events.setdefault(name, []).append((e0, e1, out.numel() * 4, z.numel() * 4, planes, act))
-        else:
-            ops.upconv3x3(*args, y_planes=planes, y_amax=ya)
+        self._timed(name + ":upconv", self.up_events, name, (out.numel() * 4, z.numel() * 4, planes, act),
+                    lambda: ops.upconv3x3(*args, y_planes=planes, y_amax=ya))
         out._prpe_amax = ya
         if planes:
             out._prpe_planes = True
@@ -377,13 +384,7 @@ class Engine:
         same chunked implicit GEMM as every other conv (and eligible for precision 3). Its
         weight is W'[co][kh*32 + kw*4 + c] = W[co, c, kh, kw] (zero for kw = 7 and c = 3)."""
         B0, _, H0, W0 = x_nchw.shape
-        key = ("stem_buf", B0, H0, W0)
-        buf = self._aux.get(key)
-        if buf is None:
-            for k in [k for k in self._aux if isinstance(k, tuple) and k[0] == "stem_buf"]:
-                del self._aux[k]                       # one batch shape at a time
-            buf = torch.zeros(B0, H0 + 6, W0 + 8, 4, device=self.device, dtype=torch.float32)
-            self._aux[key] = buf
+        buf = self._batch_buf("stem_buf", B0, (H0 + 6, W0 + 8, 4))
         amax = self.amax_slot(B0) if self.precision == 3 else None
         ops.copy_pad(ops.nhwc(x_nchw), buf[:, 3:3 + H0, 3:3 + W0, :], flip_w=flip_w, y_amax=amax)
         v = buf.as_strided((B0, H0 + 6, W0, 32), (buf.stride(0), buf.stride(1), 4, 1))
@@ -403,14 +404,8 @@ class Engine:
             y = self.empty(B0, H0 // 4, W0 // 4, stem.co)
             ya = self.amax_slot(B0)
             name = "backbone.conv1+maxpool"
-            if name in self.watch:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                ops.stem_maxpool(buf, H0, W0, amax, stem, y, ya)
-                e1.record()
-                self.events.setdefault(name, []).append((e0, e1, B0 * (H0 // 2) * (W0 // 2), stem, 3, buf.numel()))
-            else:
-                ops.stem_maxpool(buf, H0, W0, amax, stem, y, ya)
+            self._timed(name, self.events, name, (B0 * (H0 // 2) * (W0 // 2), stem, 3, buf.numel()),
+                        lambda: ops.stem_maxpool(buf, H0, W0, amax, stem, y, ya))
             y._prpe_amax = ya
             y._prpe_pooled = True
             return y
@@ -475,15 +470,8 @@ class Engine:
                  self.pk(q + ".conv3", q + ".conv3.weight", bn=q + ".bn3", act="relu"))
         y = self.empty(*x.shape[:3], packs[2].co)
         ya = self.amax_slot(x.shape[0])
-        if q in self.watch:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            ops.bottleneck(x, packs, y, x._prpe_amax, ya)
-            e1.record()
-            self.events.setdefault(q, []).append((e0, e1, x.shape[0] * x.shape[1] * x.shape[2], packs[1], 3,
-                                                  x.numel()))
-        else:
-            ops.bottleneck(x, packs, y, x._prpe_amax, ya)
+        self._timed(q, self.events, q, (x.shape[0] * x.shape[1] * x.shape[2], packs[1], 3, x.numel()),
+                    lambda: ops.bottleneck(x, packs, y, x._prpe_amax, ya))
         y._prpe_amax = ya
         return y
 
@@ -742,14 +730,7 @@ class Engine:
     # interior, the patch embedding reads the overlapping view of vit_pix4 (as the stem's buffer)
     def vit_pix4(self, B):
         H, W = arch.VIT_IMG
-        key = ("vit_pix4", B)
-        buf = self._aux.get(key)
-        if buf is None:
-            for k in [k for k in self._aux if isinstance(k, tuple) and k[0] == "vit_pix4"]:
-                del self._aux[k]                       # one batch size at a time
-            buf = torch.zeros(B, H + 4, W + 4, 4, device=self.device, dtype=torch.float32)
-            self._aux[key] = buf
-        return buf
+        return self._batch_buf("vit_pix4", B, (H + 4, W + 4, 4))
 
     def _vit_pix_out(self, B):
         if not PATCH_VIEW:

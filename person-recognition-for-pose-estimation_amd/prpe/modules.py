@@ -15,9 +15,11 @@ component (numeric names like ``adapter.0`` included), every tensor registered a
 or, for the reference's buffers (BatchNorm running statistics, AdaFace head statistics), as a
 buffer -- so ``named_parameters()`` / ``state_dict()`` of each branch carry the reference's
 own names, sharing storage with the state_dict the engine packed. These trees are the
-parameter surface only: the HIP engine computes from its packed copies, so a changed
-parameter takes effect after ``CombinedModel.load_state_dict`` (eval hot path; training is
-out of scope).
+parameter surface only: the HIP engine computes from its packed copies. An in-place write to
+a parameter (``p.add_``, ``p.copy_``, an optimizer step) bumps its version counter, which every
+``CombinedModel`` entry point checks, repacking before it computes; a write through ``p.data``
+bypasses the counter and needs ``CombinedModel.refresh_weights()`` (model.py, weight
+freshness; eval hot path, training is out of scope).
 """
 from __future__ import annotations
 

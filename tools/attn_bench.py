@@ -38,7 +38,7 @@ def main():
     q, k, v = qkv[: 4 * L].view(4, L, 3, H, D).permute(2, 0, 3, 1, 4).double().cpu()
     ref = (torch.softmax(q @ k.transpose(-1, -2) * D ** -0.5, -1) @ v).transpose(1, 2).reshape(4 * L, H * D)
     err = float((out[: 4 * L].double().cpu() - ref).abs().max())
-    print(f"PRPE_ATTN={os.environ.get('PRPE_ATTN', 'default')} max|err| {err:.2e}  attention bs={B}: {ms:.3f} ms  alg {fl / ms / 1e9:.1f} TF/s  exec {3 * fl / ms / 1e9:.1f} TF/s  "
+    print(f"max|err| {err:.2e}  attention bs={B}: {ms:.3f} ms  alg {fl / ms / 1e9:.1f} TF/s  exec {3 * fl / ms / 1e9:.1f} TF/s  "
           f"{by / ms / 1e6:.0f} GB/s (q,k,v read + o write)")
 
 
@@ -63,5 +63,4 @@ def head_major(B=256, iters=10):
 
 if __name__ == "__main__":
     main()
-    if os.environ.get("PRPE_ATTN", "64") == "64":
-        head_major()
+    head_major()
