@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PRPE_ABI_VERSION 10
+#define PRPE_ABI_VERSION 11
 
 /* activations (epilogues/prologues) */
 enum prpe_act {
@@ -395,6 +395,53 @@ int prpe_det_eval_loss(const float* boxes, const int64_t* box_strides, const flo
                        const int64_t* score_strides, int32_t B, int32_t C, int32_t N, const float* gt_boxes,
                        const int64_t* gt_batch, const int64_t* gt_classes, int32_t G, float* per_image,
                        float* loss, void* stream);
+
+/*
+ * Pose validation step after the model (PoseEstimationModule.validation_step,
+ * pose_estimation/module.py:486-502), one 256-thread workgroup per (frame, keypoint), no target
+ * tensor in memory. pred = heat, or (heat + F) * 0.5 with prpe_flip_average's F / partner / mode
+ * when heat_flipped != NULL (avg_out, optional, then receives pred; it must not overlap
+ * heat_flipped, it may be heat itself (in place) but must not overlap heat otherwise, and
+ * without heat_flipped it must be NULL).
+ *   target (_generate_target_heatmap :298-380): keypoints [B,N,K,3] = (x, y normalised, v),
+ *     mu = (x*W - 0.5, y*H - 0.5), sigma_n = sigma * clamp(sqrt(areas[b,n])/96, .5, 2) (areas
+ *     [B,N]; NULL: sigma), max over instances of exp(-(dx^2+dy^2) / (2 sigma_n^2)) * (v > 0),
+ *     / (sum_hw + 1e-8), zeroed where <= 0.005. An instance whose K visibilities are all 0 is
+ *     skipped (:348-350); weight = max over the other instances of (v == 2 ? 1 : 0.5), so an
+ *     invisible keypoint of a processed instance weighs 0.5 (:369-372).
+ *   loss (JointsMSELoss :60-111): per_kp [B,K] = mean_hw((pred - target)^2) * weight *
+ *     kp_weights[k] (host float[K]); a second launch writes loss[1] = sum_b (sum of the topk
+ *     largest per_kp[b,:]) / (B*topk) in a fixed order (no atomics: the same bits every run).
+ *   soft-argmax (_get_keypoints_from_heatmaps :237-296) of pred: coords [B,K,2], scores [B,K],
+ *     argmax (optional) exactly as prpe_softargmax gives them on pred; boxes [B,N,4] (optional):
+ *     instance 0's box scales the scores (boxes[:, 0], :501).
+ * target_out [B,K,H,W] / weights_out [B,K] (optional) receive the target and its weights.
+ * K <= 64, 1 <= N <= 256, 1 <= topk <= K; any H, W. -EINVAL launches nothing.
+ */
+int prpe_pose_eval_loss(const float* heat, const float* heat_flipped, const int32_t* partner, int32_t mode,
+                        float* avg_out, int32_t B, int32_t K, int32_t H, int32_t W, const float* keypoints,
+                        const float* areas, const float* boxes, int32_t N, float sigma, const float* kp_weights,
+                        int32_t topk, float* per_kp, float* loss, float* coords, float* scores, int32_t* argmax,
+                        float* target_out, float* weights_out, void* stream);
+
+/*
+ * COCO keypoint records of the pose validation step (pose_estimation/module.py:505-561) without
+ * host syncs. coords [B,K,2] / scores [B,K] from prpe_pose_eval_loss; boxes [B,N,4] xyxy, areas
+ * [B,N], masks / is_crowd [B,N] uint8; keep [B] uint8, a HOST array (it travels in the kernel
+ * arguments: no upload, no synchronisation) = 1 where the host has not seen the image id before
+ * in this epoch (:510-513). For a kept image b and n in range(sum(masks[b]))
+ * (the COUNT of true masks, as :516 iterates), crowd instances skipped (:517), one record:
+ *   rec_kpts [capacity,K,3] = (kx*(x2-x1) + x1, ky*(y2-y1) + y1, score > keypoint_thresh ? 2 : 1)
+ *     (fp32 multiply, then fp32 add; the comparison in double as .item() > thresh does),
+ *   rec_meta [capacity,8]  = (slot_base + b, n as int32 bits; mean of the K scores, box x 4, area).
+ * State is caller-allocated on the device as for prpe_det_metrics_update: counter uint64 [1],
+ * zeroed to reset. Records are appended in (image, instance) order at *counter; records past
+ * capacity are dropped while the counter keeps counting. K <= 64.
+ */
+int prpe_pose_coco_records(const float* coords, const float* scores, const float* boxes, const float* areas,
+                           const uint8_t* masks, const uint8_t* is_crowd, const uint8_t* keep, int32_t B,
+                           int32_t N, int32_t K, double keypoint_thresh, int32_t slot_base, uint64_t* counter,
+                           float* rec_kpts, float* rec_meta, int64_t capacity, void* stream);
 
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse

@@ -8,8 +8,9 @@ Device work: hand-written HIP kernels in ../csrc behind the C ABI of include/prp
 torch.distributed (RCCL) only.
 """
 from .arch import TASKS, state_dict_spec  # noqa: F401
+from .evalsteps import PoseEvalStep  # noqa: F401
 from .model import CombinedModel, PoseOutput  # noqa: F401
 from .postproc import keypoints_from_heatmaps, non_max_suppression, non_max_suppression_padded  # noqa: F401
 
-__all__ = ["CombinedModel", "PoseOutput", "non_max_suppression", "non_max_suppression_padded",
+__all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "non_max_suppression", "non_max_suppression_padded",
            "keypoints_from_heatmaps", "state_dict_spec", "TASKS"]

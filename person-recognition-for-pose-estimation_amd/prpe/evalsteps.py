@@ -20,9 +20,16 @@
 * ``detection_eval_loss`` — the same step's compute_loss (module_v2.py:178-303) on the eval
   head output: one block per image (confidence filter, IoU matching, the pairwise CIoU mean,
   cross-entropy, background BCE), no per-image host sync (prpe_det_eval_loss).
+* ``PoseEvalStep`` — the rest of PoseEstimationModule.validation_step (module.py:451-570) after
+  the two model passes: one launch averages the flip test in registers, rebuilds the target of
+  ``_generate_target_heatmap`` per pixel, and gives JointsMSELoss's OHKM loss and the soft-argmax
+  (prpe_pose_eval_loss); a second appends the COCO keypoint records on device
+  (prpe_pose_coco_records). The host only looks the image ids up in its set; ``predictions()``
+  reads the records once per epoch.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import ops
@@ -30,6 +37,9 @@ from .pack import pack_matrix
 
 F_NORMALIZE_EPS = 1e-12          # torch.nn.functional.normalize default eps
 COCO_FLIP_PAIRS = [(1, 2), (3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16)]  # datamodule.py:25-34
+# OKS sigmas of the 17 COCO keypoints (datamodule.py:37-40), fp32 as there
+COCO_SIGMAS = np.array([.026, .025, .025, .035, .035, .079, .079, .072, .072, .062, .062,
+                        .107, .107, .087, .087, .089, .089], dtype=np.float32)
 
 
 def flip_partner(k: int = 17, pairs=COCO_FLIP_PAIRS) -> list[int]:
@@ -133,3 +143,132 @@ def detection_eval_loss(det, gt_boxes, gt_batch, gt_labels=None):
     output ``det`` [B, 4+nc, N] (FaceDetectionModule.process_yolo_output's eval split:
     boxes det[:, :4], scores det[:, 4:]) against targets boxes / batch_idx / labels."""
     return ops.det_eval_loss(det[:, :4], det[:, 4:], gt_boxes, gt_batch, gt_labels)
+
+
+def joints_mse_keypoint_weights(sigmas=COCO_SIGMAS) -> np.ndarray:
+    """JointsMSELoss.__init__'s keypoint weights (module.py:57-58): numpy fp32 1 / (sigma + 1e-8),
+    divided by its mean (torch's mean of the same fp32 values)."""
+    w = torch.from_numpy(1 / (np.asarray(sigmas, dtype=np.float32) + 1e-8))
+    return (w / w.mean()).numpy()
+
+
+def format_coco_records(rec_kpts, rec_meta, slot_image_ids) -> list[dict]:
+    """The reference's prediction dicts (module.py:552-559) from record arrays: rec_kpts [n,K,3]
+    fp32 (x, y, v), rec_meta [n,8] fp32 whose first two columns hold int32 bits (image slot, n),
+    then score, bbox x 4, area; slot_image_ids maps a slot to its image id."""
+    kp = np.asarray(rec_kpts, dtype=np.float32)
+    meta = np.ascontiguousarray(rec_meta, dtype=np.float32)
+    slots = meta[:, :1].copy().view(np.int32)[:, 0]
+    preds = []
+    for r in range(kp.shape[0]):
+        flat = []
+        for x, y, v in kp[r].tolist():
+            flat.extend([x, y, int(v)])
+        m = meta[r].tolist()
+        preds.append({"image_id": int(slot_image_ids[slots[r]]), "category_id": 1, "keypoints": flat,
+                      "score": m[2], "bbox": m[3:7], "area": m[7]})
+    return preds
+
+
+class PoseEvalStep:
+    """PoseEstimationModule.validation_step with everything after the model on the device.
+
+    ``step = PoseEvalStep(model); step.reset(); loss = step(batch); ...; step.predictions()``.
+    ``batch`` is the reference's dict (images, keypoints [B,N,K,3], boxes [B,N,4], areas [B,N],
+    masks, is_crowd [B,N], image_ids: host values). With the batch's tensors on the device, as
+    the trainer delivers them, a step uploads nothing and never waits for the stream: the keep
+    flags of the image ids go to the record kernel as launch arguments."""
+
+    def __init__(self, model=None, heatmap_size=(64, 48), sigma: float = 2.0, keypoint_thresh: float = 0.3,
+                 ohkm_topk: int = 8, flip_mode: str = "reference", capacity: int = 1 << 16, device=None):
+        if flip_mode not in ("reference", "swap"):
+            raise ValueError(f"unknown flip mode {flip_mode!r}")
+        self.model = model
+        self.device = device if device is not None else (model.device if model is not None else "cuda")
+        self.heatmap_size = tuple(heatmap_size)
+        self.sigma = float(sigma)
+        self.keypoint_thresh = float(keypoint_thresh)
+        self.ohkm_topk = int(ohkm_topk)
+        self.flip_mode = flip_mode
+        self.capacity = int(capacity)
+        self.kp_weights = joints_mse_keypoint_weights()
+        self._state = None                # (counter, rec_kpts, rec_meta), allocated at the first batch
+        self.last = None                  # the last batch's device outputs (loss, per_kp, coords, scores)
+        self.reset()
+
+    def reset(self):
+        """on_validation_epoch_start (module.py:572-576)."""
+        self._seen = set()
+        self._slot_ids = []               # image id of every frame of the epoch, by slot
+        self._max_records = 0             # host bound on the records written (kept frames x N)
+        if self._state is not None:
+            self._state[0].zero_()
+
+    def keep_flags(self, image_ids, commit: bool = True) -> list[int]:
+        """1 where the image id was not seen before in this epoch, nor earlier in the batch
+        (module.py:507-513). The only host work of a step. ``commit`` records the ids as seen and
+        by slot; ``__call__`` does that only after both launches succeeded."""
+        if isinstance(image_ids, torch.Tensor):
+            image_ids = image_ids.tolist()
+        ids = [int(i) for i in image_ids]
+        new, keep = set(), []
+        for i in ids:
+            keep.append(0 if i in self._seen or i in new else 1)
+            new.add(i)
+        if commit:
+            self._commit(ids, new)
+        return keep
+
+    def _commit(self, ids, new):
+        self._seen |= new
+        self._slot_ids.extend(ids)
+
+    @torch.no_grad()
+    def __call__(self, batch, heatmaps=None, heatmaps_flipped=None):
+        """val_loss (a device scalar) of one batch; its records are appended on the device.
+        ``heatmaps`` (and ``heatmaps_flipped``, the flipped pass' output) skip the model."""
+        if heatmaps is None:
+            m = self.model
+            x = m._check_input(batch["images"])
+            m._sync_weights()
+            e = m.engine
+            heatmaps = e.vitpose(e.trunk(x))
+            heatmaps_flipped = e.vitpose(e.trunk(x, flip_w=True))
+        B, K, H, W = heatmaps.shape
+        if (H, W) != self.heatmap_size:
+            raise ValueError(f"PoseEvalStep: heatmaps are {H}x{W}, heatmap_size is {self.heatmap_size}")
+        if K != len(self.kp_weights):
+            raise ValueError(f"PoseEvalStep: {K} heatmap channels, {len(self.kp_weights)} keypoint weights")
+        dev = heatmaps.device
+        kp, boxes, areas = (batch[k].to(dev, torch.float32) for k in ("keypoints", "boxes", "areas"))
+        N = kp.shape[1]
+        if self._state is None:
+            self._state = (torch.zeros(1, dtype=torch.int64, device=dev),
+                           torch.empty(self.capacity, K, 3, device=dev), torch.empty(self.capacity, 8, device=dev))
+        slot_base = len(self._slot_ids)
+        keep = self.keep_flags(batch["image_ids"], commit=False)
+        if len(keep) != B:
+            raise ValueError(f"PoseEvalStep: {len(keep)} image ids for {B} frames")
+        out = ops.pose_eval_loss(heatmaps, kp, self.kp_weights, heat_flipped=heatmaps_flipped,
+                                 partner=flip_partner(K), mode=0 if self.flip_mode == "reference" else 1,
+                                 areas=areas, boxes=boxes, sigma=self.sigma, topk=self.ohkm_topk)
+        ops.pose_coco_records(out["coords"], out["scores"], boxes, areas, batch["masks"].to(dev),
+                              batch["is_crowd"].to(dev), keep, self.keypoint_thresh, slot_base, *self._state)
+        self.keep_flags(batch["image_ids"])           # both launches are queued: the ids are now seen
+        self._max_records += sum(keep) * N
+        self.last = out
+        return out["loss"][0]
+
+    def predictions(self) -> list[dict]:
+        """The epoch's eval_predictions (module.py:552-561), one device-to-host read."""
+        if self._state is None:
+            return []
+        counter, kpts, meta = self._state
+        n = min(self._max_records, self.capacity)
+        K = kpts.shape[1]
+        flat = torch.cat([kpts[:n].reshape(-1), meta[:n].reshape(-1), counter.view(torch.float32)]).cpu().numpy()
+        count = int(flat[-2:].view(np.int64)[0])
+        if count > self.capacity:
+            raise RuntimeError(f"PoseEvalStep: {count} records exceed the capacity {self.capacity}")
+        return format_coco_records(flat[:n * K * 3].reshape(n, K, 3)[:count],
+                                   flat[n * K * 3:n * (K * 3 + 8)].reshape(n, 8)[:count], self._slot_ids)

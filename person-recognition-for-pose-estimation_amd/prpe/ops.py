@@ -369,3 +369,78 @@ def det_eval_loss(boxes, scores, gt_boxes, gt_batch, gt_classes=None):
                                    B, Cn, N, gt.data_ptr(), gb.data_ptr(), _ptr(gc), gt.shape[0], per.data_ptr(),
                                    loss.data_ptr(), _stream()), "prpe_det_eval_loss")
     return loss, per
+
+
+def pose_eval_loss(heat, keypoints, kp_weights, *, heat_flipped=None, partner=None, mode=0, areas=None, boxes=None,
+                   sigma=2.0, topk=8, avg_out=None, want_avg=False, want_argmax=False, want_target=False):
+    """Fused pose validation step after the model (see include/prpe.h): heat [B,K,H,W] (+ the
+    flipped pass' heat_flipped, averaged in registers), keypoints [B,N,K,3], areas [B,N] / boxes
+    [B,N,4] optional, kp_weights host floats [K]. Returns a dict: loss [1], per_kp [B,K], coords
+    [B,K,2], scores [B,K], and on request avg, argmax, target + weights."""
+    heat, keypoints = _gpu(heat, keypoints)
+    heat = heat.contiguous()
+    assert heat.dtype == torch.float32, heat.dtype
+    B, K, H, W = heat.shape
+    dev = heat.device
+    kp = keypoints.to(torch.float32).contiguous()
+    assert kp.dim() == 4 and kp.shape[0] == B and kp.shape[2] == K and kp.shape[3] == 3, kp.shape
+    N = kp.shape[1]
+    if heat_flipped is not None:
+        heat_flipped = _gpu(heat_flipped).contiguous()
+        assert heat_flipped.shape == heat.shape and heat_flipped.dtype == torch.float32, heat_flipped.dtype
+        if want_avg and avg_out is None:
+            avg_out = torch.empty_like(heat)
+    if avg_out is not None:
+        assert avg_out.shape == heat.shape and avg_out.is_contiguous() and avg_out.dtype == torch.float32
+    ar = None if areas is None else _gpu(areas).to(torch.float32).contiguous()
+    bx = None if boxes is None else _gpu(boxes).to(torch.float32).contiguous()
+    assert ar is None or tuple(ar.shape) == (B, N)
+    assert bx is None or tuple(bx.shape) == (B, N, 4)
+    if len(kp_weights) != K:
+        raise ValueError(f"pose_eval_loss: {len(kp_weights)} keypoint weights for K = {K}")
+    kw = (C.c_float * K)(*[float(v) for v in kp_weights])
+    pa = None if partner is None else (C.c_int32 * K)(*[int(v) for v in partner])
+    out = {"loss": torch.empty(1, device=dev), "per_kp": torch.empty(B, K, device=dev),
+           "coords": torch.empty(B, K, 2, device=dev), "scores": torch.empty(B, K, device=dev)}
+    if avg_out is not None:
+        out["avg"] = avg_out
+    if want_argmax:
+        out["argmax"] = torch.empty(B, K, device=dev, dtype=torch.int32)
+    if want_target:
+        out["target"] = torch.empty_like(heat)
+        out["weights"] = torch.empty(B, K, device=dev)
+    check(lib().prpe_pose_eval_loss(heat.data_ptr(), _ptr(heat_flipped), pa, mode, _ptr(avg_out), B, K, H, W,
+                                    kp.data_ptr(), _ptr(ar), _ptr(bx), N, float(sigma), kw, topk,
+                                    out["per_kp"].data_ptr(), out["loss"].data_ptr(), out["coords"].data_ptr(),
+                                    out["scores"].data_ptr(), _ptr(out.get("argmax")), _ptr(out.get("target")),
+                                    _ptr(out.get("weights")), _stream()), "prpe_pose_eval_loss")
+    return out
+
+
+def pose_coco_records(coords, scores, boxes, areas, masks, is_crowd, keep, keypoint_thresh, slot_base, counter,
+                      rec_kpts, rec_meta):
+    """Append one batch's COCO keypoint records to the device state (see include/prpe.h):
+    counter uint64 [1] (an int64 tensor), rec_kpts [cap,K,3], rec_meta [cap,8]. ``keep`` is a
+    HOST sequence of B flags: it goes into the kernel arguments, so nothing is uploaded."""
+    _gpu(coords, scores, boxes, areas, masks, is_crowd, counter, rec_kpts, rec_meta)
+    B, K, two = coords.shape
+    N = boxes.shape[1]
+    assert two == 2 and coords.is_contiguous() and scores.is_contiguous() and tuple(scores.shape) == (B, K)
+    assert coords.dtype == torch.float32 and scores.dtype == torch.float32
+    bx = boxes.to(torch.float32).contiguous()
+    ar = areas.to(torch.float32).contiguous()
+    mk = masks.to(torch.uint8).contiguous()         # bool -> 0/1
+    cr = is_crowd.to(torch.uint8).contiguous()
+    if isinstance(keep, torch.Tensor):
+        raise ValueError("pose_coco_records: keep is a host sequence of flags, not a tensor")
+    kf = (C.c_uint8 * len(keep))(*[1 if v else 0 for v in keep])
+    assert tuple(bx.shape) == (B, N, 4) and tuple(ar.shape) == (B, N) and tuple(mk.shape) == (B, N)
+    assert tuple(cr.shape) == (B, N) and len(keep) == B
+    cap = rec_kpts.shape[0]
+    assert counter.dtype == torch.int64 and counter.numel() == 1
+    assert rec_kpts.dtype == torch.float32 and rec_kpts.is_contiguous() and tuple(rec_kpts.shape) == (cap, K, 3)
+    assert rec_meta.dtype == torch.float32 and rec_meta.is_contiguous() and tuple(rec_meta.shape) == (cap, 8)
+    check(lib().prpe_pose_coco_records(coords.data_ptr(), scores.data_ptr(), bx.data_ptr(), ar.data_ptr(),
+                                       mk.data_ptr(), cr.data_ptr(), kf, B, N, K, float(keypoint_thresh),
+                                       int(slot_base), counter.data_ptr(), rec_kpts.data_ptr(), rec_meta.data_ptr(),
+                                       cap, _stream()), "prpe_pose_coco_records")
