@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PRPE_ABI_VERSION 11
+#define PRPE_ABI_VERSION 12
 
 /* activations (epilogues/prologues) */
 enum prpe_act {
@@ -442,6 +442,46 @@ int prpe_pose_coco_records(const float* coords, const float* scores, const float
                            const uint8_t* masks, const uint8_t* is_crowd, const uint8_t* keep, int32_t B,
                            int32_t N, int32_t K, double keypoint_thresh, int32_t slot_base, uint64_t* counter,
                            float* rec_kpts, float* rec_meta, int64_t capacity, void* stream);
+
+/*
+ * Top-down pose: person boxes -> ViTPose crops -> keypoints in frame pixels, all on the device
+ * (csrc/topdown.hip). The reference has no runnable crop stage
+ * (pose_estimation/datamodule_v2.py leans on packages that are not part of it), so the semantics
+ * are defined here; the resample equals torch's grid_sample(bilinear, zeros, align_corners=False).
+ *
+ * crop_meta [max_crops][8] float: frame index and detection row as int32 bits (as rec_meta), the
+ * window x0, y0, w, h in frame pixels, the detection score, one spare column (0).
+ *
+ * select: dets [B, max_det, 6] + counts [B] from the padded NMS (rows in descending score order).
+ *   A frame's candidates are its first rows with score >= score_thr, at most max_per_frame of them;
+ *   of these a row is skipped when a scaled coordinate (x * box_scale_x, y * box_scale_y) or its
+ *   window is not finite or a scaled side is below min_size. counts[b] < 0 (NMS candidate
+ *   overflow): nothing from b, status bit 0. Slots go in (frame, row) order by a scan inside one
+ *   workgroup: the same list every run. Crops past max_crops are dropped from the end, status bit
+ *   1. n_crops [1] = slots filled; slots at or past it get frame index -1 (other columns 0).
+ *   Window, fp32, in this order (a = 192/256): cx = (x1+x2)*0.5, cy = (y1+y2)*0.5; w = x2-x1,
+ *   h = y2-y1; w > a*h ? h = w/a : w = h*a; w *= pad, h *= pad; x0 = cx - 0.5*w, y0 = cy - 0.5*h.
+ *   H, W (the frame, 1..2^24) are validated only: a window is not clipped to the frame.
+ * resize: frames = a strided view [B, H, W, 3] (any strides, e.g. NCHW frames permuted);
+ *   crops = the contiguous, 16-byte aligned, zero-bordered NHWC4 buffer [max_crops, 260, 196, 4].
+ *   Slot s < *n_crops: crops[s, 2+i, 2+j, 0:3] = bilinear sample at
+ *   (x0 + (j+0.5)*w/192 - 0.5, y0 + (i+0.5)*h/256 - 0.5), taps outside the frame 0. Slots at or
+ *   past *n_crops (and slots whose frame index is outside [0, B)): interior zeros. The border is
+ *   never written; channel 3 only ever receives 0. n_crops and crop_meta are read on the device.
+ * keypoints: coords [n, K, 2] in [0,1] of the crop + scores [n, K] (prpe_softargmax on the crops'
+ *   heatmaps), n <= max_crops the slots the pose net ran on. kpts [max_crops, K, 3] =
+ *   (x0 + cx*w, y0 + cy*h, score) (fp32 product, then sum) for slots below min(*n_crops, n),
+ *   zeros above.
+ * -EINVAL launches nothing.
+ */
+int prpe_crop_select(const float* dets, const int32_t* counts, int32_t B, int32_t max_det, float score_thr,
+                     int32_t max_per_frame, float min_size, float box_scale_x, float box_scale_y, int32_t H,
+                     int32_t W, float pad, int32_t max_crops, float* crop_meta, int32_t* n_crops, int32_t* status,
+                     void* stream);
+int prpe_crop_resize(const prpe_view* frames, const float* crop_meta, const int32_t* n_crops, int32_t max_crops,
+                     float* crops, void* stream);
+int prpe_crop_keypoints(const float* coords, const float* scores, int32_t n, int32_t K, const float* crop_meta,
+                        const int32_t* n_crops, int32_t max_crops, float* kpts, void* stream);
 
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse

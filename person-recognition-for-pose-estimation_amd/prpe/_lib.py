@@ -14,7 +14,7 @@ from ._srchash import source_hash
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libprpe.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class PrpeError(RuntimeError):
@@ -97,6 +97,9 @@ SIGNATURES = {
     "prpe_pose_eval_loss": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _F,
                                       C.POINTER(C.c_float), _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "prpe_pose_coco_records": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_double, _I, _P, _P, _P, _L, _P]),
+    "prpe_crop_select": (C.c_int, [_P, _P, _I, _I, _F, _I, _F, _F, _F, _I, _I, _F, _I, _P, _P, _P, _P]),
+    "prpe_crop_resize": (C.c_int, [_VP, _P, _P, _I, _P, _P]),
+    "prpe_crop_keypoints": (C.c_int, [_P, _P, _I, _I, _P, _P, _I, _P, _P]),
     "prpe_abi_version": (C.c_int, []),
     "prpe_build_info": (C.c_char_p, []),
     "prpe_source_hash": (C.c_char_p, []),

@@ -27,6 +27,8 @@ for _cin, _d, _n in ((64, 64, 3), (64, 128, 4), (128, 256, 14), (256, 512, 3)):
 RESNET50_STAGES = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))
 
 YOLO_WIDTH = (3, 16, 32, 64, 128, 256)
+YOLO_IMG = (160, 160)        # the CustomYOLO adapter's output (modify_models.py:40-71): the image its
+                             # YOLO net sees, so eval boxes are in these units whatever the frame size
 VIT_HIDDEN, VIT_LAYERS, VIT_HEADS, VIT_MLP = 768, 12, 12, 3072
 VIT_IMG = (256, 192)
 VIT_PATCH = 16

@@ -565,7 +565,7 @@ class Engine:
         t = self.conv(feat, self.pk(a + ".0", a + ".0.weight", bn=a + ".1", bias_key=a + ".0.bias", act="silu"),
                       prec=self.feat_prec(feat))
         p7 = self.pk(a + ".7", a + ".7.weight", bn=a + ".8", bias_key=a + ".7.bias", act="silu")
-        u = self.upconv(a + ".4", t, a + ".4.weight", (160, 160), True, bn=a + ".5", bias_key=a + ".4.bias",
+        u = self.upconv(a + ".4", t, a + ".4.weight", arch.YOLO_IMG, True, bn=a + ".5", bias_key=a + ".4.bias",
                         act="silu", planes=True)
         t = self.conv(u, p7, planes_out=True)
         p10 = self.pk(a + ".10", a + ".10.weight", 1, 1, bn=a + ".11", bias_key=a + ".10.bias", act="silu")
@@ -740,6 +740,23 @@ class Engine:
         out = buf[:, 2:2 + H, 2:2 + W, :3]
         out._prpe_pix4 = buf
         return out
+
+    def crop_pix4(self, n):
+        """The top-down crops (prpe.topdown): the zero-bordered NHWC4 buffer [n, 260, 196, 4]
+        prpe_crop_resize fills. A kind of its own: _batch_buf keeps one batch size per kind, so
+        sharing vit_pix4's would reallocate whenever whole-frame pose (batch B) and top-down pose
+        (batch max_crops) alternate."""
+        H, W = arch.VIT_IMG
+        return self._batch_buf("crop_pix4", n, (H + 4, W + 4, 4))
+
+    @staticmethod
+    def pix4_interior(buf):
+        """The pixel_values view [n, 256, 192, 3] of a pix4 buffer (or of its first n slots),
+        tagged so that vit_backbone reads the buffer in place instead of copying into vit_pix4."""
+        H, W = arch.VIT_IMG
+        pix = buf[:, 2:2 + H, 2:2 + W, :3]
+        pix._prpe_pix4 = buf
+        return pix
 
     def _lin(self, name, wkey, bkey, act="none"):
         p = self._packs.get(name)

@@ -11,6 +11,7 @@ import ctypes as C
 import torch
 
 from ._lib import ACT, RES_NONE, BneckDesc, ConvDesc, PrpeError, StemDesc, View, check, lib
+from .arch import VIT_IMG
 
 
 def _stream() -> C.c_void_p:
@@ -444,3 +445,97 @@ def pose_coco_records(coords, scores, boxes, areas, masks, is_crowd, keep, keypo
                                        mk.data_ptr(), cr.data_ptr(), kf, B, N, K, float(keypoint_thresh),
                                        int(slot_base), counter.data_ptr(), rec_kpts.data_ptr(), rec_meta.data_ptr(),
                                        cap, _stream()), "prpe_pose_coco_records")
+
+
+# ------------------------------------------------------------------ top-down pose (csrc/topdown.hip)
+CROP_META_COLS = 8
+CROP_BORDER = 2                      # the patch conv's padding = the crop buffer's zero border
+
+
+def _check_dev(what, name, t, dtype, shape=None, min_numel=None):
+    """A contiguous device tensor of ``dtype`` and exactly ``shape`` (or at least ``min_numel``
+    elements): the top-down kernels index these by slot / frame with no strides, so a short or
+    strided one would be read or written out of bounds on the device. Raised here, on the host."""
+    ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+    if ok and shape is not None:
+        ok = tuple(t.shape) == tuple(shape)
+    if ok and min_numel is not None:
+        ok = t.numel() >= min_numel
+    if not ok:
+        want = f"{list(shape)}" if shape is not None else f"[>= {min_numel}]"
+        got = (f"{type(t).__name__}" if not isinstance(t, torch.Tensor) else
+               f"{t.dtype} {list(t.shape)} on {t.device}, contiguous={t.is_contiguous()}")
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} device tensor {want}, got {got}")
+
+
+def crop_select(dets, counts, frame_hw, *, crop_meta, n_crops, status, score_thr=0.25, max_per_frame=8,
+                min_size=4.0, box_scale=(1.0, 1.0), pad=1.25):
+    """Padded NMS output -> the crop list (prpe_crop_select, include/prpe.h): dets [B, max_det, 6],
+    counts [B] int32; ``frame_hw`` = (H, W) of the frames, ``box_scale`` = (x, y) detector units
+    -> frame pixels. Fills crop_meta [max_crops, 8], n_crops [1] int32, status [1] int32 (bit 0:
+    a frame's NMS overflowed, bit 1: crops dropped past max_crops). No host read."""
+    what = "prpe_crop_select"
+    if not (isinstance(dets, torch.Tensor) and dets.dim() == 3 and dets.shape[2] == 6):
+        raise ValueError(f"{what}: dets must be [B, max_det, 6]")
+    B, max_det, _ = dets.shape
+    _check_dev(what, "dets", dets, torch.float32, (B, max_det, 6))
+    _check_dev(what, "counts", counts, torch.int32, (B,))
+    if not (isinstance(crop_meta, torch.Tensor) and crop_meta.dim() == 2):
+        raise ValueError(f"{what}: crop_meta must be [max_crops, {CROP_META_COLS}]")
+    max_crops = crop_meta.shape[0]
+    _check_dev(what, "crop_meta", crop_meta, torch.float32, (max_crops, CROP_META_COLS))
+    _check_dev(what, "n_crops", n_crops, torch.int32, (1,))
+    _check_dev(what, "status", status, torch.int32, (1,))
+    H, W = (int(v) for v in frame_hw)
+    sx, sy = (float(v) for v in box_scale)
+    if B < 1 or max_det < 1 or max_crops < 1 or max_per_frame < 1 or H < 1 or W < 1:
+        raise ValueError(f"{what}: empty batch, crop list or frame")
+    check(lib().prpe_crop_select(dets.data_ptr(), counts.data_ptr(), B, max_det, float(score_thr), int(max_per_frame),
+                                 float(min_size), sx, sy, H, W, float(pad), max_crops, crop_meta.data_ptr(),
+                                 n_crops.data_ptr(), status.data_ptr(), _stream()), what)
+    return crop_meta, n_crops, status
+
+
+def crop_resize(frames, crop_meta, n_crops, crops):
+    """Resample the windows of ``crop_meta`` from ``frames`` ([B, 3, H, W] float32 device, any
+    strides) into the interior of ``crops``, the zero-bordered NHWC4 buffer [max_crops, 260, 196, 4]
+    (Engine.crop_pix4; prpe_crop_resize, include/prpe.h). Slots at or past n_crops are zeroed."""
+    what = "prpe_crop_resize"
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.float32 and
+            frames.dim() == 4 and frames.shape[1] == 3 and frames.numel() > 0):
+        raise ValueError(f"{what}: frames must be a float32 device tensor [B, 3, H, W]")
+    if not (isinstance(crop_meta, torch.Tensor) and crop_meta.dim() == 2):
+        raise ValueError(f"{what}: crop_meta must be [max_crops, {CROP_META_COLS}]")
+    max_crops = crop_meta.shape[0]
+    shape =(max_crops, VIT_IMG[0] + 2 * CROP_BORDER, VIT_IMG[1] + 2 * CROP_BORDER, 4)
+    _check_dev(what, "crop_meta", crop_meta, torch.float32, (max_crops, CROP_META_COLS))
+    _check_dev(what, "n_crops", n_crops, torch.int32, (1,))
+    _check_dev(what, "crops", crops, torch.float32, shape)
+    if max_crops < 1 or crops.data_ptr() % 16:
+        raise ValueError(f"{what}: crops must hold at least one slot and be 16-byte aligned")
+    check(lib().prpe_crop_resize(C.byref(view(nhwc(frames))), crop_meta.data_ptr(), n_crops.data_ptr(), max_crops,
+                                 crops.data_ptr(), _stream()), what)
+    return crops
+
+
+def crop_keypoints(coords, scores, crop_meta, n_crops, kpts):
+    """Soft-argmax output of the first n slots (coords [n, K, 2] in [0,1] of the crop, scores
+    [n, K]) -> kpts [max_crops, K, 3] = (x, y in frame pixels, score); slots at or past
+    min(n_crops, n) are zeroed (prpe_crop_keypoints, include/prpe.h)."""
+    what = "prpe_crop_keypoints"
+    if not (isinstance(coords, torch.Tensor) and coords.dim() == 3 and coords.shape[2] == 2):
+        raise ValueError(f"{what}: coords must be [n, K, 2]")
+    n, K, _ = coords.shape
+    if not (isinstance(crop_meta, torch.Tensor) and crop_meta.dim() == 2):
+        raise ValueError(f"{what}: crop_meta must be [max_crops, {CROP_META_COLS}]")
+    max_crops = crop_meta.shape[0]
+    _check_dev(what, "coords", coords, torch.float32, (n, K, 2))
+    _check_dev(what, "scores", scores, torch.float32, (n, K))
+    _check_dev(what, "crop_meta", crop_meta, torch.float32, (max_crops, CROP_META_COLS))
+    _check_dev(what, "n_crops", n_crops, torch.int32, (1,))
+    _check_dev(what, "kpts", kpts, torch.float32, (max_crops, K, 3))
+    if n < 1 or K < 1 or n > max_crops:
+        raise ValueError(f"{what}: {n} crops of keypoints for a list of {max_crops} slots")
+    check(lib().prpe_crop_keypoints(coords.data_ptr(), scores.data_ptr(), n, K, crop_meta.data_ptr(),
+                                    n_crops.data_ptr(), max_crops, kpts.data_ptr(), _stream()), what)
+    return kpts
