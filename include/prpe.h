@@ -294,7 +294,8 @@ int prpe_attention_strided(const float* qkv, int64_t s_frame, int64_t s_which, i
  *   out[c, i] = sum_j v[c, j] softmax_j(q[:, i] . k[:, j] * scale)
  * qkv view [N, h, w, nh*(2*dk+dh)] (per head: q dk | k dk | v dh), out view [N,h,w,nh*dh].
  * vout (optional, ptr may be NULL): v gathered head-major [N,h,w,nh*dh] — the
- * ``v.reshape(b, c, h, w)`` operand of the depthwise positional conv (nn.py:122). */
+ * ``v.reshape(b, c, h, w)`` operand of the depthwise positional conv (nn.py:122).
+ * out (and vout) must have qkv's N, h and w: any other map size is PRPE_EINVAL. */
 int prpe_psa_attention(const prpe_view* qkv, const prpe_view* out, const prpe_view* vout,
                        int32_t nh, int32_t dk, int32_t dh, float scale, void* stream);
 

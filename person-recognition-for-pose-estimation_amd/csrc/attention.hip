@@ -635,6 +635,9 @@ extern "C" int prpe_psa_attention(const prpe_view* qkv, const prpe_view* out, co
                                   int32_t dk, int32_t dh, float scale, void* stream) {
   if (!view_ok(qkv) || !view_ok(out) || nh <= 0 || dk <= 0 || dh <= 0) return PRPE_EINVAL;
   if (qkv->c != nh * (2 * dk + dh) || out->c != nh * dh || qkv->n != out->n) return PRPE_EINVAL;
+  // both kernels walk qkv's h x w tokens and write out at the same (h, w): a smaller out would be
+  // written out of bounds
+  if (out->h != qkv->h || out->w != qkv->w) return PRPE_EINVAL;
   const int L = qkv->h * qkv->w;
   const size_t shm = sizeof(float) * (size_t)nh * L * L;
   prpe_view vo{};

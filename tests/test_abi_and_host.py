@@ -39,6 +39,15 @@ def test_invalid_arguments_are_rejected_before_launch():
     assert L.prpe_attention(None, None, 1, 192, 12, 64, 0.125, None) == -22
     bad = _lib.View(0x1000, 1, 4, 4, 8, 128, 32, 8, 1)
     assert L.prpe_norm_sigmoid(C.byref(bad), C.byref(bad), None) == -22    # > 4 channels
+    # PSA attention writes out at qkv's (h, w): an out (or vout) of another map size is refused,
+    # on the LDS kernel's sizes (5x5) and on the streaming kernel's (20x20)
+    for h, w in ((5, 5), (20, 20)):
+        qkv = _lib.View(0x1000, 2, h, w, 256, h * w * 256, w * 256, 256, 1)
+        for oh, ow in ((h - 1, w), (h, w - 1), (h + 1, w), (w, h + 1), (1, 1)):
+            o = _lib.View(0x1000, 2, oh, ow, 128, oh * ow * 128, ow * 128, 128, 1)
+            assert L.prpe_psa_attention(C.byref(qkv), C.byref(o), None, 2, 32, 64, 0.2, None) == -22, (h, w, oh, ow)
+            ok = _lib.View(0x1000, 2, h, w, 128, h * w * 128, w * 128, 128, 1)
+            assert L.prpe_psa_attention(C.byref(qkv), C.byref(ok), C.byref(o), 2, 32, 64, 0.2, None) == -22
     # precision 3 without its fp16 planes / input max bound, or with a prologue affine
     v = _lib.View(0x1000, 1, 4, 4, 32, 512, 128, 32, 1)
     d = _lib.ConvDesc(x=v, y=v, kh=1, kw=1, stride=1, pad=0, w_hi=0x1000, w_lo=0x1000, w_lo2=0x1000,
