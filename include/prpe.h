@@ -484,6 +484,61 @@ int prpe_crop_resize(const prpe_view* frames, const float* crop_meta, const int3
 int prpe_crop_keypoints(const float* coords, const float* scores, int32_t n, int32_t K, const float* crop_meta,
                         const int32_t* n_crops, int32_t max_crops, float* kpts, void* stream);
 
+/*
+ * uint8 frames in (csrc/ingest.hip): what a camera, a decoder or a dataloader hands
+ * over -- uint8 HWC images at the source resolution, RGB or BGR -- resized, normalised and written
+ * straight into the buffer the next kernel reads. The reference resizes with cv2 (A.Resize +
+ * A.Normalize, object_detection/datamodule.py:78-100, pose_estimation/datamodule.py:374-395), whose
+ * uint8 fixed-point rounding is not restated here; the semantics are this project's: half-pixel-
+ * centre bilinear, no antialias, per-channel affine, all in fp32 on the raw 0..255 values.
+ *
+ * A strided 4-D uint8 view, logical shape [n, h, w, c], strides in elements (= bytes): an HWC
+ * batch, NCHW frames through a permute, a slice of a wider tensor.
+ */
+typedef struct prpe_view_u8 {
+  const uint8_t* ptr;
+  int32_t n, h, w, c;
+  int64_t sn, sh, sw, sc;
+} prpe_view_u8;
+
+/*
+ * frame_ingest: frames [B, Hs, Ws, 3] uint8 -> y, the interior [B, H, W, 4] of the stem's
+ * zero-bordered NHWC4 buffer (4 contiguous channels, 16-byte aligned, strides multiples of 4
+ * floats: what the 16-byte path of the strided copy asks of its destination). The geometry comes
+ * from the host: the region (top, left, nh, nw) inside H x W; stretch is (0, 0, H, W), a letterbox
+ * a centred region (prpe/ingest.py).
+ *   Inside the region, pixel (i, j) samples the source at
+ *     sx = clamp((j - left + 0.5) * (Ws / nw) - 0.5, 0, Ws - 1),
+ *     sy = clamp((i - top  + 0.5) * (Hs / nh) - 0.5, 0, Hs - 1)      (edges replicate: torch's
+ *   F.interpolate(bilinear, align_corners=False, antialias=False)). Coordinates in fp64, each
+ *   weight ax = sx - floor(sx), ay rounded to fp32 once; on the raw values, fp32:
+ *     t = v00 + ax * (v01 - v00), u = v10 + ax * (v11 - v10), raw = t + ay * (u - t).
+ *   y[.., c] = raw * a[c] + b[c], an fp32 multiply, then an fp32 add (never fused): at nh == Hs and
+ *   nw == Ws the output has the bits of torch's u8.float() * a + b. swap_rb != 0: output channel c
+ *   reads source channel 2 - c (BGR sources); a, b, fill are indexed by the OUTPUT channel.
+ *   Outside the region: y[.., c] = fill[c] * a[c] + b[c] (fill in raw units). Channel 3 = 0, in the
+ *   same 16-byte store. The buffer's border is never addressed.
+ * a, b, fill: HOST arrays of 3 floats; they travel in the kernel arguments (no upload).
+ * y_amax (optional): device [B], y_amax[n] raised to max|y[n]| over the whole interior, fill
+ *   pixels included (zeroed by the caller).
+ * -EINVAL, nothing launched: a null pointer, frames->c != 3, frames->n != y->n, a source or
+ *   destination side below 1 (or a source side above 2^24), y not 4 contiguous 16-byte aligned
+ *   channels, a region that is empty or not inside H x W, a grid past 31 bits. No argument makes
+ *   the kernel read outside the source: coordinates are clamped before they become indices.
+ *
+ * crop_resize_u8: the crop stage above (same crop_meta, n_crops, window arithmetic, [-2, size+1]
+ * clamp, empty-slot and frame-index handling, same destination) reading uint8 frames [B, H, W, 3]:
+ * taps outside the frame contribute raw 0, and every pixel of a filled slot is raw * a[c] + b[c]
+ * (as above; swap_rb as above). Empty slots are exact zeros. With a = 1, b = 0 the crops have the
+ * bits the fp32 crop stage gives on the same frames converted to float.
+ */
+int prpe_frame_ingest(const prpe_view_u8* frames, const prpe_view* y, int32_t top, int32_t left, int32_t nh,
+                      int32_t nw, const float* a, const float* b, const float* fill, int32_t swap_rb,
+                      float* y_amax /* optional */, void* stream);
+int prpe_crop_resize_u8(const prpe_view_u8* frames, const float* crop_meta, const int32_t* n_crops,
+                        int32_t max_crops, const float* a, const float* b, int32_t swap_rb, float* crops,
+                        void* stream);
+
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse
  * a library built from other sources than the ones beside it. */

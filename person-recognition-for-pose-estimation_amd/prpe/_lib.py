@@ -22,6 +22,7 @@ class PrpeError(RuntimeError):
 
 
 class View(C.Structure):
+    """prpe_view (float32) and prpe_view_u8 (uint8 source frames): the same layout, strides in elements."""
     _fields_ = [("ptr", C.c_void_p),
                 ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32),
                 ("sn", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64), ("sc", C.c_int64)]
@@ -100,6 +101,9 @@ SIGNATURES = {
     "prpe_crop_select": (C.c_int, [_P, _P, _I, _I, _F, _I, _F, _F, _F, _I, _I, _F, _I, _P, _P, _P, _P]),
     "prpe_crop_resize": (C.c_int, [_VP, _P, _P, _I, _P, _P]),
     "prpe_crop_keypoints": (C.c_int, [_P, _P, _I, _I, _P, _P, _I, _P, _P]),
+    "prpe_frame_ingest": (C.c_int, [_VP, _VP, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float), _I, _P, _P]),
+    "prpe_crop_resize_u8": (C.c_int, [_VP, _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P]),
     "prpe_abi_version": (C.c_int, []),
     "prpe_build_info": (C.c_char_p, []),
     "prpe_source_hash": (C.c_char_p, []),

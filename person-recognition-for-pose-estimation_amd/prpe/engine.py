@@ -387,6 +387,24 @@ class Engine:
         buf = self._batch_buf("stem_buf", B0, (H0 + 6, W0 + 8, 4))
         amax = self.amax_slot(B0) if self.precision == 3 else None
         ops.copy_pad(ops.nhwc(x_nchw), buf[:, 3:3 + H0, 3:3 + W0, :], flip_w=flip_w, y_amax=amax)
+        return self._stem_conv(buf, amax, H0, W0, pool)
+
+    def stem_u8(self, frames_u8, ingest, pool=False):
+        """``stem`` on uint8 source frames [B, Hs, Ws, 3] (any strides): prpe_frame_ingest resizes,
+        pads and normalises them (``ingest``: a prpe.ingest.FrameIngest) straight into the same
+        zero-bordered NHWC4 buffer, raising the same per-frame max|x| slots; no fp32 frames exist
+        in between. Everything after the fill is ``stem``'s."""
+        B0, Hs, Ws, _ = frames_u8.shape
+        H0, W0 = ingest.size
+        buf = self._batch_buf("stem_buf", B0, (H0 + 6, W0 + 8, 4))
+        amax = self.amax_slot(B0) if self.precision == 3 else None
+        ops.frame_ingest(frames_u8, buf[:, 3:3 + H0, 3:3 + W0, :], ingest.geometry(Hs, Ws), ingest.a, ingest.b,
+                         ingest.fill, ingest.swap_rb, y_amax=amax)
+        return self._stem_conv(buf, amax, H0, W0, pool)
+
+    def _stem_conv(self, buf, amax, H0, W0, pool):
+        """What follows the fill of the stem buffer: the strided view, the pack, the conv (+ pool)."""
+        B0 = buf.shape[0]
         v = buf.as_strided((B0, H0 + 6, W0, 32), (buf.stride(0), buf.stride(1), 4, 1))
         v._prpe_amax = amax
         stem = self._packs.get("backbone.conv1")
@@ -411,8 +429,18 @@ class Engine:
             return y
         return self.conv(v, stem)
 
+    def trunk_u8(self, frames_u8, ingest):
+        """``trunk`` on uint8 source frames [B, Hs, Ws, 3] (``stem_u8``): the same kernels from the
+        stem conv on, so the same bits as ``trunk`` on fp32 frames holding what the ingest wrote."""
+        with self.prec("trunk"):
+            y = self._trunk_layers(self.stem_u8(frames_u8, ingest, pool=True))
+            y._prpe_amax_tag = ("trunk", self._amax_epoch.get("trunk"))
+            return y
+
     def _trunk(self, x_nchw, flip_w=False):
-        y = self.stem(x_nchw, flip_w, pool=True)
+        return self._trunk_layers(self.stem(x_nchw, flip_w, pool=True))
+
+    def _trunk_layers(self, y):
         if getattr(y, "_prpe_pooled", False):
             x = y
         else:

@@ -30,6 +30,7 @@ import torch
 
 from . import arch, ops
 from .engine import Engine
+from .ingest import FrameIngest
 from .modules import branch_trees
 
 
@@ -150,8 +151,32 @@ class CombinedModel:
     def forward(self, x):
         x = self._check_input(x)
         self._sync_weights()
+        return self._task_head(self.engine.trunk(x))
+
+    __call__ = forward
+
+    @torch.no_grad()
+    def forward_u8(self, frames_u8, ingest=None):
+        """``forward`` on uint8 source frames [B, Hs, Ws, 3] on the device (any strides: an HWC
+        batch, NCHW frames through ``permute(0, 2, 3, 1)``), at the source resolution. ``ingest``:
+        a prpe.FrameIngest (default: letterbox to 640 x 640, raw / 255, RGB); prpe_frame_ingest
+        resizes and normalises them straight into the stem's buffer."""
+        frames_u8, ingest = self._check_input_u8(frames_u8, ingest)
+        self._sync_weights()
+        return self._task_head(self.engine.trunk_u8(frames_u8, ingest))
+
+    def _check_input_u8(self, x, ingest):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4
+                and x.shape[3] == 3 and x.numel() > 0):
+            raise ValueError("expected uint8 CUDA(HIP) frames [B,Hs,Ws,3]")
+        if ingest is None:
+            ingest = FrameIngest()
+        if not isinstance(ingest, FrameIngest):
+            raise ValueError(f"ingest must be a prpe.FrameIngest, got {type(ingest).__name__}")
+        return x, ingest
+
+    def _task_head(self, feat):
         e = self.engine
-        feat = e.trunk(x)
         t = self.current_task
         if t == "pose_estimation":
             return PoseOutput(heatmaps=e.vitpose(feat))
@@ -160,8 +185,6 @@ class CombinedModel:
         if t == "face_detection":
             return e.yolo("yolo_face", feat, self._stride(self.yolo_face))
         return e.adaface(feat)
-
-    __call__ = forward
 
     @torch.no_grad()
     def vitpose_from_pixels(self, pixel_values):
@@ -199,8 +222,17 @@ class CombinedModel:
         Same kernels, same arithmetic: results are bit-identical to the sequential order."""
         x = self._check_input(x)
         self._sync_weights()
+        return self._all_heads(self.engine.trunk(x), face_stride, concurrent)
+
+    @torch.no_grad()
+    def forward_all_u8(self, frames_u8, ingest=None, face_stride=None, concurrent=True):
+        """``forward_all`` on uint8 source frames [B, Hs, Ws, 3] (see ``forward_u8``)."""
+        frames_u8, ingest = self._check_input_u8(frames_u8, ingest)
+        self._sync_weights()
+        return self._all_heads(self.engine.trunk_u8(frames_u8, ingest), face_stride, concurrent)
+
+    def _all_heads(self, feat, face_stride, concurrent):
         e = self.engine
-        feat = e.trunk(x)
         stride = face_stride if face_stride is not None else self._stride(self.yolo_face)
         heads = (lambda: e.yolo("yolo_face", feat, stride), lambda: e.adaface(feat), lambda: e.vitpose(feat))
         if not concurrent:

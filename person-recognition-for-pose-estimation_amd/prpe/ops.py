@@ -2,7 +2,8 @@
 
 Tensors are float32 on the GPU with a *logical NHWC* shape [N, H, W, C] and arbitrary
 strides (channel slices of concat buffers, NCHW inputs via ``permute``, broadcast
-residuals with stride 0 ...). Every call launches on the current torch stream.
+residuals with stride 0 ...); the source frames of ``frame_ingest`` / ``crop_resize_u8`` are uint8
+[N, H, W, 3]. Every call launches on the current torch stream.
 """
 from __future__ import annotations
 
@@ -539,3 +540,72 @@ def crop_keypoints(coords, scores, crop_meta, n_crops, kpts):
     check(lib().prpe_crop_keypoints(coords.data_ptr(), scores.data_ptr(), n, K, crop_meta.data_ptr(),
                                     n_crops.data_ptr(), max_crops, kpts.data_ptr(), _stream()), what)
     return kpts
+
+
+# ------------------------------------------------------------------ uint8 frames in (csrc/ingest.hip)
+def _u8_frames(what, frames):
+    """prpe_view_u8 of source frames: a uint8 device tensor with the logical shape [B, Hs, Ws, 3]
+    and any strides (an HWC batch, NCHW through ``permute(0, 2, 3, 1)``, a slice). Dtype, channel
+    count and device are checked here, before the C ABI."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+        raise ValueError(f"{what}: frames must be a uint8 tensor, got "
+                         f"{getattr(frames, 'dtype', type(frames).__name__)}")
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError(f"{what}: frames must be [B, Hs, Ws, 3] (3 channels last; permute NCHW frames), got "
+                         f"{list(frames.shape)}")
+    if not frames.is_cuda:
+        raise ValueError(f"{what}: frames must be a HIP device tensor, got one on {frames.device}")
+    n, h, w, c = frames.shape
+    return View(frames.data_ptr(), n, h, w, c, *frames.stride())
+
+
+def _f3(what, name, v):
+    v = [float(x) for x in v]
+    if len(v) != 3:
+        raise ValueError(f"{what}: {name} must hold 3 floats (one per output channel)")
+    return (C.c_float * 3)(*v)
+
+
+def frame_ingest(frames, y, region, a, b, fill=(0.0, 0.0, 0.0), swap_rb=False, y_amax=None):
+    """uint8 frames [B, Hs, Ws, 3] (any strides) -> ``y``, the interior [B, H, W, 4] of a
+    zero-bordered NHWC4 buffer (Engine.stem's): bilinear resize into ``region`` = (top, left, nh,
+    nw), ``fill`` (raw 0..255 units) outside it, then raw * a[c] + b[c]; channel 3 = 0
+    (prpe_frame_ingest, include/prpe.h). ``a``, ``b``, ``fill``: 3 host floats each. ``swap_rb``:
+    the source is BGR. ``y_amax`` ([B] device, zeroed): raised to max|y[n]| per frame."""
+    what = "prpe_frame_ingest"
+    fv = _u8_frames(what, frames)
+    if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 4):
+        raise ValueError(f"{what}: y must be a float32 device tensor [B, H, W, 4]")
+    if y.shape[0] != frames.shape[0] or y.shape[3] != 4 or y.stride(3) != 1 or y.data_ptr() % 16 or \
+            any(s % 4 for s in y.stride()[:3]):
+        raise ValueError(f"{what}: y must be [{frames.shape[0]}, H, W, 4] with 4 contiguous, 16-byte aligned "
+                         f"channels, got {list(y.shape)} strides {list(y.stride())}")
+    top, left, nh, nw = (int(v) for v in region)
+    if nh < 1 or nw < 1 or top < 0 or left < 0 or top + nh > y.shape[1] or left + nw > y.shape[2]:
+        raise ValueError(f"{what}: region {(top, left, nh, nw)} is empty or not inside {list(y.shape[1:3])}")
+    _check_slots(what, frames.shape[0], y_amax)
+    check(lib().prpe_frame_ingest(C.byref(fv), C.byref(view(y)), top, left, nh, nw, _f3(what, "a", a),
+                                  _f3(what, "b", b), _f3(what, "fill", fill), int(bool(swap_rb)), _ptr(y_amax),
+                                  _stream()), what)
+    return y
+
+
+def crop_resize_u8(frames, crop_meta, n_crops, crops, a=(1.0, 1.0, 1.0), b=(0.0, 0.0, 0.0), swap_rb=False):
+    """``crop_resize`` from uint8 source frames [B, Hs, Ws, 3] (any strides), every pixel of a
+    filled slot then raw * a[c] + b[c] (prpe_crop_resize_u8, include/prpe.h); the windows of
+    ``crop_meta`` are in the pixels of these frames."""
+    what = "prpe_crop_resize_u8"
+    fv = _u8_frames(what, frames)
+    if not (isinstance(crop_meta, torch.Tensor) and crop_meta.dim() == 2):
+        raise ValueError(f"{what}: crop_meta must be [max_crops, {CROP_META_COLS}]")
+    max_crops = crop_meta.shape[0]
+    shape = (max_crops, VIT_IMG[0] + 2 * CROP_BORDER, VIT_IMG[1] + 2 * CROP_BORDER, 4)
+    _check_dev(what, "crop_meta", crop_meta, torch.float32, (max_crops, CROP_META_COLS))
+    _check_dev(what, "n_crops", n_crops, torch.int32, (1,))
+    _check_dev(what, "crops", crops, torch.float32, shape)
+    if max_crops < 1 or crops.data_ptr() % 16:
+        raise ValueError(f"{what}: crops must hold at least one slot and be 16-byte aligned")
+    check(lib().prpe_crop_resize_u8(C.byref(fv), crop_meta.data_ptr(), n_crops.data_ptr(), max_crops,
+                                    _f3(what, "a", a), _f3(what, "b", b), int(bool(swap_rb)), crops.data_ptr(),
+                                    _stream()), what)
+    return crops

@@ -55,26 +55,75 @@ class TopDownPose:
         m = self.model
         x = m._check_input(frames)
         m._sync_weights()
-        e = m.engine
         B, _, H, W = x.shape
-        if dets.dim() != 3 or dets.shape[0] != B or counts.shape != (B,):
-            raise ValueError(f"dets [B, max_det, 6] and counts [B] must match the {B} frames")
-        cap = int(self.max_crops) if self.max_crops is not None else B * self.max_per_frame
+        scale = self.box_scale
+        if scale is None:
+            scale = (W / arch.YOLO_IMG[1], H / arch.YOLO_IMG[0])
+        return self._crops_to_keypoints(B, (H, W), dets, counts, scale,
+                                        lambda meta, n_crops, buf: ops.crop_resize(x, meta, n_crops, buf))
+
+    @torch.no_grad()
+    def from_frames_u8(self, frames_u8, ingest=None):
+        """uint8 source frames [B, Hs, Ws, 3] on the device (any strides) -> the same output, with
+        detections, windows and keypoints in SOURCE pixels: ``ingest`` (a prpe.FrameIngest) resizes
+        the frames for the trunk and the person head, the boxes go back to source pixels on the
+        device, and the crops are resampled from the source frames themselves
+        (prpe_crop_resize_u8, with the ingest's a, b and channel order), which hold 2-3x the
+        pixels per person of the model frame. ``dets`` in the output are in source pixels."""
+        m = self.model
+        frames_u8, ingest = m._check_input_u8(frames_u8, ingest)
+        m._sync_weights()
+        e = m.engine
+        det = e.yolo(self.branch, e.trunk_u8(frames_u8, ingest), m._stride(getattr(m, self.branch)))
+        dets, counts = non_max_suppression_padded(det)
+        # detector units -> model-frame pixels -> source pixels; rows past counts[b] may hold anything
+        H, W = ingest.size
         scale = self.box_scale
         if scale is None:
             scale = (W / arch.YOLO_IMG[1], H / arch.YOLO_IMG[0])
         elif isinstance(scale, (int, float)):
             scale = (scale, scale)
-        dev = x.device
+        sx, sy = (float(v) for v in scale)
+        Hs, Ws = frames_u8.shape[1:3]
+        boxes = dets[..., :4].clone()
+        boxes[..., 0::2] *= sx
+        boxes[..., 1::2] *= sy
+        dets = torch.cat([ingest.to_source(boxes, Hs, Ws), dets[..., 4:]], 2)
+        return self.from_detections_u8(frames_u8, dets, counts, ingest)
+
+    @torch.no_grad()
+    def from_detections_u8(self, frames_u8, dets, counts, ingest=None):
+        """Enter after NMS with uint8 source frames: ``dets`` [B, max_det, 6] in SOURCE pixels
+        (``box_scale`` is not applied) and counts [B] int32. Only the ingest's a, b and channel
+        order are used (the crops come from the source frames, not from the model frame)."""
+        m = self.model
+        frames_u8, ingest = m._check_input_u8(frames_u8, ingest)
+        m._sync_weights()
+        B, Hs, Ws, _ = frames_u8.shape
+        return self._crops_to_keypoints(
+            B, (Hs, Ws), dets, counts, 1.0,
+            lambda meta, n_crops, buf: ops.crop_resize_u8(frames_u8, meta, n_crops, buf, ingest.a, ingest.b,
+                                                          ingest.swap_rb))
+
+    def _crops_to_keypoints(self, B, frame_hw, dets, counts, scale, resize):
+        """crop list -> ``resize(meta, n_crops, buf)`` fills the crop buffer -> ViTPose -> keypoints
+        in the pixels of the frames the windows refer to."""
+        e = self.model.engine
+        if dets.dim() != 3 or dets.shape[0] != B or counts.shape != (B,):
+            raise ValueError(f"dets [B, max_det, 6] and counts [B] must match the {B} frames")
+        cap = int(self.max_crops) if self.max_crops is not None else B * self.max_per_frame
+        if isinstance(scale, (int, float)):
+            scale = (scale, scale)
+        dev = dets.device
         meta = torch.empty(cap, ops.CROP_META_COLS, device=dev, dtype=torch.float32)
         n_crops = torch.empty(1, device=dev, dtype=torch.int32)
         status = torch.empty(1, device=dev, dtype=torch.int32)
         kpts = torch.empty(cap, arch.NUM_KEYPOINTS, 3, device=dev, dtype=torch.float32)
-        ops.crop_select(dets, counts, (H, W), crop_meta=meta, n_crops=n_crops, status=status,
+        ops.crop_select(dets, counts, frame_hw, crop_meta=meta, n_crops=n_crops, status=status,
                         score_thr=self.score_thr, max_per_frame=self.max_per_frame, min_size=self.min_size,
                         box_scale=scale, pad=self.pad)
         buf = e.crop_pix4(cap)
-        ops.crop_resize(x, meta, n_crops, buf)
+        resize(meta, n_crops, buf)
         n = cap
         if self.compact:
             n = int(n_crops.item())                # the only host read (and synchronisation)
