@@ -49,9 +49,12 @@ __global__ __launch_bounds__(256) void ce_argmax_kernel(const float* logits, int
   __shared__ float s_v[4];
   __shared__ int s_i[4];
   __shared__ double s_d[4];
+  // a thread starts from its first column, so a row of -inf still names a column (ties go to the
+  // smaller index: column 0, as torch.max); a thread with no column keeps (-inf, none)
   float bv = -INFINITY;
   int bi = 0x7fffffff;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+  if ((int)threadIdx.x < C) { bv = x[threadIdx.x]; bi = threadIdx.x; }
+  for (int c = threadIdx.x + blockDim.x; c < C; c += blockDim.x) {
     const float v = x[c];
     const bool better = (v != v) ? !(bv != bv) : (v > bv);   // first NaN wins, then strict >
     if (better) { bv = v; bi = c; }
