@@ -539,6 +539,49 @@ int prpe_crop_resize_u8(const prpe_view_u8* frames, const float* crop_meta, cons
                         int32_t max_crops, const float* a, const float* b, int32_t swap_rb, float* crops,
                         void* stream);
 
+/*
+ * Face identification: a gallery of enrolled embeddings and a fused cosine top-k search
+ * (csrc/gallery.hip). The reference lists face_identification among its tasks
+ * (scripts/modify_models.py:331) but has no gallery code; the semantics are this project's.
+ *
+ * Gallery storage (the search kernel's operand, caller-allocated, 16-byte aligned): fp32
+ * [capacity][D] holding the L2-normalised rows, D x 4 bytes per row and nothing else -- the search
+ * runs on the fp32-input matrix cores, so the operands are exact fp32 (no bf16 planes, no third
+ * plane). norms [capacity] fp32 holds each row's norm before normalisation. D is a multiple of 32
+ * in [32, 512].
+ *
+ * enrol: x [n][D] fp32 with row stride x_row_stride (elements, >= D) -> gallery rows
+ *   [row0, row0 + n) and norms [row0, row0 + n): norm = ||x||, row = x / max(norm, 1e-12) with
+ *   prpe_l2norm's arithmetic (F.normalize; a zero row stays zero). On the device, no host copy;
+ *   no other row is touched, and a row's bytes do not depend on n, row0 or its neighbours.
+ *
+ * topk: queries [Q][D] fp32 with row stride q_row_stride, normalised inside as above, against
+ *   gallery rows [0, G). valid (optional) [G] bytes: a row whose byte is 0 is skipped. k in 1..8.
+ *   score(q, g) = the fp32 dot product of the two normalised rows. Candidates are ordered by score
+ *   descending, then row ascending; a candidate whose score is not finite (a NaN or infinite
+ *   element on either side) is skipped. scores [Q][k] fp32 and rows [Q][k] int32 receive each
+ *   query's best k in that order; slots past the number of candidates hold row -1, score -inf.
+ *   labels (int64 [G]) and ident (int64 [Q]) go together (both or neither):
+ *   ident[q] = labels[rows[q][0]] when rows[q][0] >= 0 and scores[q][0] >= threshold, else -1.
+ *   A (query, row) score is the same bits whatever the row's index, G, Q or the other queries of
+ *   the launch (one fixed fma order over the columns), so exact duplicate rows tie exactly and
+ *   the lower index wins. No atomics: two runs give the same bits.
+ *   workspace: >= prpe_gallery_topk_workspace_bytes(Q, G, k) bytes, 256-byte aligned (the
+ *   normalised queries and one k-list per query and gallery chunk; the [Q][G] score matrix is never
+ *   stored). Concurrent calls on different streams must pass different workspaces.
+ * -EINVAL, nothing launched: a null pointer (valid, and labels + ident as a pair, may be null), n,
+ *   Q, G or capacity below 1, G above 2^31 - 4097, k outside 1..8, D not a multiple of 32 in
+ *   [32, 512], row0 < 0 or row0 + n > capacity, a row stride below D, labels without ident or the
+ *   reverse, a misaligned gallery or workspace, a workspace that is too small.
+ */
+int prpe_gallery_enrol(const float* x, int64_t x_row_stride, int32_t n, int32_t D, float* gallery, float* norms,
+                       int32_t capacity, int32_t row0, void* stream);
+int64_t prpe_gallery_topk_workspace_bytes(int32_t Q, int32_t G, int32_t k);
+int prpe_gallery_topk(const float* queries, int64_t q_row_stride, int32_t Q, int32_t D, const float* gallery,
+                      int32_t G, const uint8_t* valid, int32_t k, float* scores, int32_t* rows,
+                      const int64_t* labels, float threshold, int64_t* ident, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse
  * a library built from other sources than the ones beside it. */

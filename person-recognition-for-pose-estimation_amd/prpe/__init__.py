@@ -9,10 +9,12 @@ torch.distributed (RCCL) only.
 """
 from .arch import TASKS, state_dict_spec  # noqa: F401
 from .evalsteps import PoseEvalStep  # noqa: F401
+from .gallery import FaceGallery, FaceIdentifier  # noqa: F401
 from .ingest import FrameIngest  # noqa: F401
 from .model import CombinedModel, PoseOutput  # noqa: F401
 from .postproc import keypoints_from_heatmaps, non_max_suppression, non_max_suppression_padded  # noqa: F401
 from .topdown import TopDownPose  # noqa: F401
 
-__all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "TopDownPose", "FrameIngest", "non_max_suppression",
+__all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "TopDownPose", "FrameIngest", "FaceGallery", "FaceIdentifier",
+           "non_max_suppression",
            "non_max_suppression_padded", "keypoints_from_heatmaps", "state_dict_spec", "TASKS"]

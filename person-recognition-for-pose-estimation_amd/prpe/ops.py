@@ -609,3 +609,91 @@ def crop_resize_u8(frames, crop_meta, n_crops, crops, a=(1.0, 1.0, 1.0), b=(0.0,
                                     _f3(what, "a", a), _f3(what, "b", b), int(bool(swap_rb)), crops.data_ptr(),
                                     _stream()), what)
     return crops
+
+
+# ------------------------------------------------------------------ face identification (csrc/gallery.hip)
+GALLERY_MAX_K = 8
+GALLERY_MAX_DIM = 512
+GALLERY_STEP_ROWS = 64               # gallery rows a workgroup takes per step: 4 waves x one 16-row MFMA tile
+
+
+def gallery_plan(Q, G):
+    """(query block width, query blocks, rows per chunk, chunks) of a search of ``Q`` queries over
+    ``G`` rows: the host-side launch plan of prpe_gallery_topk restated (csrc/gallery.hip,
+    ``gallery_plan``). The results never depend on it; tests use it to aim at chunk boundaries."""
+    qb = 16 if Q <= 16 else 64
+    nqb = -(-Q // qb)
+    tiles = -(-G // GALLERY_STEP_ROWS)
+    target = 1024 if Q <= 16 else max(512 // nqb, 1)
+    tpc = -(-tiles // target)
+    return qb, nqb, tpc * GALLERY_STEP_ROWS, -(-tiles // tpc)
+
+
+def _gallery_dim(what, D):
+    if D % 32 or not 32 <= D <= GALLERY_MAX_DIM:
+        raise ValueError(f"{what}: the embedding width must be a multiple of 32 in [32, {GALLERY_MAX_DIM}], got {D}")
+
+
+def gallery_enrol(x, gallery, norms, row0=0):
+    """L2-normalise the rows of ``x`` [n, D] (float32 device, contiguous) into ``gallery`` [capacity, D]
+    at rows row0 .. row0 + n, their norms into ``norms`` [capacity] (prpe_gallery_enrol,
+    include/prpe.h). No other row is touched; nothing is read back."""
+    what = "prpe_gallery_enrol"
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and isinstance(gallery, torch.Tensor) and gallery.dim() == 2):
+        raise ValueError(f"{what}: x must be [n, D] and gallery [capacity, D]")
+    n, D = x.shape
+    capacity = gallery.shape[0]
+    _gallery_dim(what, D)
+    _check_dev(what, "x", x, torch.float32, (n, D))
+    _check_dev(what, "gallery", gallery, torch.float32, (capacity, D))
+    _check_dev(what, "norms", norms, torch.float32, (capacity,))
+    row0 = int(row0)
+    if n < 1 or row0 < 0 or row0 + n > capacity or gallery.data_ptr() % 16:
+        raise ValueError(f"{what}: rows [{row0}, {row0 + n}) do not fit a 16-byte aligned gallery of {capacity} rows")
+    check(lib().prpe_gallery_enrol(x.data_ptr(), D, n, D, gallery.data_ptr(), norms.data_ptr(), capacity, row0,
+                                   _stream()), what)
+    return gallery, norms
+
+
+def gallery_topk(queries, gallery, G, k, *, scores, rows, valid=None, labels=None, threshold=0.0, ident=None,
+                 workspace=None):
+    """Cosine top-k of ``queries`` [Q, D] against rows [0, G) of ``gallery`` [capacity, D]
+    (prpe_gallery_topk, include/prpe.h): fills scores [Q, k] float32 and rows [Q, k] int32, ordered
+    by score descending then row ascending; (-inf, -1) past the number of candidates. ``valid``
+    [>= G] uint8: 0 skips the row. With ``labels`` [>= G] int64 and ``ident`` [Q] int64:
+    ident[q] = labels[rows[q, 0]] when scores[q, 0] >= threshold, else -1. ``workspace``: a uint8
+    device tensor of at least prpe_gallery_topk_workspace_bytes(Q, G, k) bytes (allocated here when
+    None). No host read."""
+    what = "prpe_gallery_topk"
+    if not (isinstance(queries, torch.Tensor) and queries.dim() == 2 and isinstance(gallery, torch.Tensor) and
+            gallery.dim() == 2):
+        raise ValueError(f"{what}: queries must be [Q, D] and gallery [capacity, D]")
+    Q, D = queries.shape
+    capacity = gallery.shape[0]
+    G, k = int(G), int(k)
+    _gallery_dim(what, D)
+    if Q < 1 or not 1 <= G <= capacity or not 1 <= k <= GALLERY_MAX_K:
+        raise ValueError(f"{what}: Q = {Q}, G = {G} of {capacity} rows, k = {k} (1..{GALLERY_MAX_K})")
+    _check_dev(what, "queries", queries, torch.float32, (Q, D))
+    _check_dev(what, "gallery", gallery, torch.float32, (capacity, D))
+    _check_dev(what, "scores", scores, torch.float32, (Q, k))
+    _check_dev(what, "rows", rows, torch.int32, (Q, k))
+    if valid is not None:
+        _check_dev(what, "valid", valid, torch.uint8, min_numel=G)
+    if (labels is None) != (ident is None):
+        raise ValueError(f"{what}: labels and ident go together")
+    if labels is not None:
+        _check_dev(what, "labels", labels, torch.int64, min_numel=G)
+        _check_dev(what, "ident", ident, torch.int64, (Q,))
+    nbytes = lib().prpe_gallery_topk_workspace_bytes(Q, G, k)
+    if nbytes < 0:
+        raise ValueError(f"{what}: prpe_gallery_topk_workspace_bytes({Q}, {G}, {k}) failed")
+    if workspace is None:
+        workspace = torch.empty(nbytes, device=queries.device, dtype=torch.uint8)
+    _check_dev(what, "workspace", workspace, torch.uint8, min_numel=nbytes)
+    if gallery.data_ptr() % 16 or workspace.data_ptr() % 256:
+        raise ValueError(f"{what}: the gallery must be 16-byte and the workspace 256-byte aligned")
+    check(lib().prpe_gallery_topk(queries.data_ptr(), D, Q, D, gallery.data_ptr(), G, _ptr(valid), k,
+                                  scores.data_ptr(), rows.data_ptr(), _ptr(labels), float(threshold), _ptr(ident),
+                                  workspace.data_ptr(), workspace.numel(), _stream()), what)
+    return scores, rows
