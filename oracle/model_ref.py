@@ -367,10 +367,12 @@ def nms_single(boxes: Tensor, scores: Tensor, thr: float, max_keep: int | None =
     return nms_restated(boxes, scores, thr, max_keep)
 
 
-def non_max_suppression(outputs: Tensor, confidence_threshold=0.001, iou_threshold=0.65):
+def non_max_suppression(outputs: Tensor, confidence_threshold=0.001, iou_threshold=0.65, max_det=300,
+                        max_nms=30000):
     """yolopt.util.non_max_suppression (training/yolopt/util.py:123-169) without the
-    wall-clock cut-off (:133-134,166-167, non-deterministic). outputs [B, 4+nc, N]."""
-    max_wh, max_det, max_nms = 7680, 300, 30000
+    wall-clock cut-off (:133-134,166-167, non-deterministic). outputs [B, 4+nc, N].
+    ``max_det`` / ``max_nms`` default to the reference's hard-coded 300 / 30000 (util.py:126)."""
+    max_wh = 7680
     bs = outputs.shape[0]
     nc = outputs.shape[1] - 4
     xc = outputs[:, 4:4 + nc].amax(1) > confidence_threshold
