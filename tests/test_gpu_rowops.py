@@ -86,11 +86,14 @@ def dev_in(t, stride=None, shift=0):
 def nhwc_layout(n, h, w, c, kind):
     """(stride, shift) of a logical NHWC view: dense, the interior of a larger NHWC buffer with 4
     more channels per pixel (16-byte alignment kept), the same with 5 more channels and an odd
-    start (nothing aligned), or a permuted NCHW tensor."""
+    start (nothing aligned), a permuted NCHW tensor, or (concat) channels [8, 8 + c) of a dense
+    NHWC buffer of c + 16 channels: pixels, rows and frames stay linear at a pixel stride > c."""
     if kind == "dense":
         return (h * w * c, w * c, c, 1), 0
     if kind == "nchw":
         return (c * h * w, w, 1, h * w), 0
+    if kind == "concat":
+        return (h * w * (c + 16), w * (c + 16), c + 16, 1), 8
     pc = 4 if kind == "inner" else 5
     sw = c + pc
     sh = (w + 2) * sw
