@@ -60,16 +60,24 @@ __global__ __launch_bounds__(PE_THREADS) void pose_eval_kernel(PoseEvalK p) {
     for (int j = 0; j < p.K; ++j) any |= kpn[j * 3 + 2] > 0.f;
     const float vis = kpn[k * 3 + 2];
     if (any) wc = vis == 2.f ? 1.f : 0.5f;        // a skipped instance adds no weight (:348-350)
-    s_act[tid] = any && vis > 0.f;
-    s_mx[tid] = kpn[k * 3] * (float)W - 0.5f;
-    s_my[tid] = kpn[k * 3 + 1] * (float)p.H - 0.5f;
+    const float mx = kpn[k * 3] * (float)W - 0.5f, my = kpn[k * 3 + 1] * (float)p.H - 0.5f;
+    s_mx[tid] = mx;
+    s_my[tid] = my;
     float sg = p.sigma;
     if (p.areas) {
       float w = sqrtf(p.areas[(int64_t)b * p.N + tid]) / 96.f;
       w = w < 0.5f ? 0.5f : (w > 2.f ? 2.f : w);
       sg = p.sigma * w;
     }
-    s_den[tid] = 2.f * (sg * sg);
+    const float den = 2.f * (sg * sg);
+    s_den[tid] = den;
+    // 1: draws keypoint k. The reference multiplies the Gaussian of a keypoint it does not draw by
+    // a mask of 0 (:361-363), and NaN * 0 is NaN: a processed instance with a NaN sigma (a
+    // negative area) or a NaN centre wipes the map of such a keypoint too. 2: masked, but the
+    // Gaussian may not be a number (anything but a finite centre over a finite positive 2 sigma^2)
+    const bool plain = den > 0.f && den <= 3.402823466e38f && fabsf(mx) <= 3.402823466e38f &&
+                       fabsf(my) <= 3.402823466e38f;
+    s_act[tid] = !any ? 0 : (vis > 0.f ? 1 : (plain ? 0 : 2));
   }
   wc = warp_max(wc);
   if (lane == 0) rw[wave] = wc;
@@ -105,7 +113,8 @@ __global__ __launch_bounds__(PE_THREADS) void pose_eval_kernel(PoseEvalK p) {
     for (int n = 0; n < p.N; ++n) {
       if (!s_act[n]) continue;
       const float dx = fx - s_mx[n], dy = fy - s_my[n];
-      const float g = expf(-(dx * dx + dy * dy) / s_den[n]);
+      float g = expf(-(dx * dx + dy * dy) / s_den[n]);
+      if (s_act[n] == 2) g *= 0.f;                  // the mask of a keypoint that is not drawn: 0, or NaN
       if (g > t || g != g) t = g;                   // torch.maximum: NaN propagates
     }
     return t;

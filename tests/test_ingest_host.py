@@ -15,13 +15,14 @@ from conftest import ROOT
 from prpe import FrameIngest, _lib
 
 
-def ingest_ref(u8, ingest, dtype=torch.float64):
+def ingest_ref(u8, ingest, dtype=torch.float64, region=None):
     """prpe_frame_ingest in plain torch on the host: u8 [B, Hs, Ws, 3] (source channel order) ->
     [B, H, W, 3] of ``dtype``: F.interpolate(bilinear, align_corners=False, antialias=False) of the
-    raw values into the region, the fill outside it, then raw * a + b."""
+    raw values into the region (``ingest.geometry``'s, or the given (top, left, nh, nw)), the fill
+    outside it, then raw * a + b."""
     B, Hs, Ws, _ = u8.shape
     H, W = ingest.size
-    top, left, nh, nw = ingest.geometry(Hs, Ws)
+    top, left, nh, nw = ingest.geometry(Hs, Ws) if region is None else region
     x = u8.cpu().permute(0, 3, 1, 2).to(dtype)
     if ingest.swap_rb:
         x = x.flip(1)
@@ -123,6 +124,95 @@ def test_ingest_ref_letterbox_fill_and_identity():
     assert torch.equal(y[:, 2:6], u8.float() * a + b)
     fill = torch.tensor(ing.fill) * a + b
     assert torch.equal(y[:, :2], fill.expand(2, 2, 8, 3)) and torch.equal(y[:, 6:], fill.expand(2, 2, 8, 3))
+
+
+# ---------------------------------------------------------------------------------- the edges
+# name -> ((Hs, Ws) of the source, (H, W) of the model frame, region (top, left, nh, nw)): the
+# frame_ingest shapes tests/test_gpu_framestages.py sends to the kernel
+INGEST_EDGES = {
+    "source_1x1": ((1, 1), (5, 7), (0, 0, 5, 7)),               # xb == xa and yb == ya everywhere
+    "source_one_row": ((1, 9), (6, 11), (0, 0, 6, 11)),         # Hs == 1
+    "source_one_column": ((9, 1), (11, 6), (0, 0, 11, 6)),      # Ws == 1
+    "region_one_row": ((5, 40), (8, 16), (3, 0, 1, 16)),        # nh == 1: the source's middle row
+    "region_one_column": ((40, 5), (8, 16), (0, 5, 8, 1)),      # nw == 1
+    "strong_downscale": ((97, 131), (3, 5), (0, 0, 3, 5)),
+    "odd_region_off_every_edge": ((10, 14), (16, 24), (3, 5, 9, 11)),
+    "narrow_with_whole_row_groups": ((10, 14), (16, 40), (0, 0, 16, 40)),   # W < 256, H == 2 * 8
+    # region = source size: every weight is 0 and the result is the source pixel
+    "identity_1x1": ((1, 1), (1, 1), (0, 0, 1, 1)),
+    "identity_whole_row_groups": ((16, 40), (16, 40), (0, 0, 16, 40)),
+    "identity_odd_region": ((9, 11), (16, 24), (3, 5, 9, 11)),
+}
+
+
+def edge_source(name):
+    Hs, Ws = INGEST_EDGES[name][0]
+    g = torch.Generator().manual_seed(31 + sorted(INGEST_EDGES).index(name))
+    u8 = torch.randint(0, 256, (2, Hs, Ws, 3), generator=g, dtype=torch.uint8)
+    u8[0, 0, 0, 0], u8[1, -1, -1, 2] = 255, 0
+    return u8
+
+
+def ingest_plain(u8, size, region, a, b, fill):
+    """The resize rule as a Python loop in float64, written apart from ``ingest_ref``: an output
+    pixel centre (i + 0.5) maps to (i + 0.5) * Hs / nh - 0.5 in the source, clamped below at 0;
+    the second tap is the next pixel or, on the last one, the same; weights 1 - t and t, the
+    horizontal pair first (torch's upsample_bilinear2d with align_corners=False)."""
+    import math
+    B, Hs, Ws, _ = u8.shape
+    H, W = size
+    top, left, nh, nw = region
+    out = torch.empty(B, H, W, 3, dtype=torch.float64)
+    src = u8.double()
+    for i in range(H):
+        for j in range(W):
+            if not (top <= i < top + nh and left <= j < left + nw):
+                for c in range(3):
+                    out[:, i, j, c] = fill[c] * a[c] + b[c]
+                continue
+            sy = max((i - top + 0.5) * (Hs / nh) - 0.5, 0.0)
+            sx = max((j - left + 0.5) * (Ws / nw) - 0.5, 0.0)
+            ya, xa = min(math.floor(sy), Hs - 1), min(math.floor(sx), Ws - 1)
+            yb, xb = min(ya + 1, Hs - 1), min(xa + 1, Ws - 1)
+            ty, tx = sy - ya, sx - xa
+            for c in range(3):
+                p, q = src[:, ya, xa, c] * (1 - tx) + src[:, ya, xb, c] * tx, \
+                    src[:, yb, xa, c] * (1 - tx) + src[:, yb, xb, c] * tx
+                out[:, i, j, c] = (p * (1 - ty) + q * ty) * a[c] + b[c]
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(INGEST_EDGES))
+def test_ingest_ref_at_the_edges_equals_the_plain_statement(name):
+    """``ingest_ref`` (F.interpolate in float64) against ``ingest_plain`` at the degenerate
+    geometries. Both are float64 throughout but order the four products differently, so they
+    agree to a few fp64 roundings at 255, not bit for bit: the bound is 2^-40 raw units, 2^-26 of
+    the 2^-14 the kernel is held to. Fill pixels are exact."""
+    (Hs, Ws), size, region = INGEST_EDGES[name]
+    u8 = edge_source(name)
+    ing = FrameIngest(size=size, mode="stretch", norm=RAW, fill=(114, 3, 250))
+    ref = ingest_ref(u8, ing, region=region)
+    plain = ingest_plain(u8, size, region, ing.a, ing.b, ing.fill)
+    assert ref.shape == plain.shape == (2, *size, 3)
+    assert float((ref - plain).abs().max()) <= 2.0 ** -40
+    top, left, nh, nw = region
+    inside = torch.zeros(size, dtype=torch.bool)
+    inside[top:top + nh, left:left + nw] = True
+    assert torch.equal(ref[:, ~inside], plain[:, ~inside])
+    if not bool(inside.all()):
+        assert torch.equal(ref[0][~inside][0], torch.tensor(ing.fill, dtype=torch.float64))
+    assert float(ref[:, inside].max()) > 150.0 and float(ref[:, inside].min()) >= 0.0
+    # one source row / column: every output row / column of the region is the same, to the
+    # yardstick's own fp64 rounding (its weights 1 - t and t need not sum to 1 exactly)
+    if Hs == 1:
+        assert float((ref[:, top:top + nh] - ref[:, top:top + 1]).abs().max()) <= 2.0 ** -40
+    if Ws == 1:
+        assert float((ref[:, :, left:left + nw] - ref[:, :, left:left + 1]).abs().max()) <= 2.0 ** -40
+    if (Hs, Ws) == (1, 1):
+        assert float((ref - u8.double().expand(2, *size, 3)).abs().max()) <= 2.0 ** -40
+    if name == "region_one_row":                      # (0 + 0.5) * 5 / 1 - 0.5 = 2: source row 2, weight 0
+        sub = FrameIngest(size=(1, 16), mode="stretch", norm=RAW)
+        assert torch.equal(ref[:, 3:4], ingest_ref(u8[:, 2:3], sub))
 
 
 # ---------------------------------------------------------------------------------- ABI

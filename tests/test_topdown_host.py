@@ -173,6 +173,155 @@ def test_select_negative_count_and_truncation_set_status():
     assert _frames_rows(meta, n) == [(0, 0), (0, 1), (1, 0), (2, 0), (2, 1), (2, 2)]
 
 
+# ---------------------------------------------------------------------------------- the edges
+NAN, INF = float("nan"), float("inf")
+
+
+def _below(v):
+    """The next fp32 below ``v`` (a Python float)."""
+    return float(torch.nextafter(_f(v), _f(-INF)))
+
+
+def _above(v):
+    return float(torch.nextafter(_f(v), _f(INF)))
+
+
+def select_edge_cases():
+    """The crop_select edge cases that tests/test_gpu_framestages.py sends to the kernel: name ->
+    (dets, counts, keyword arguments, expected n_crops, expected status, expected (frame, row)
+    list). The expectations are literals worked out by hand from include/prpe.h's rule; this file
+    holds ``select_ref`` and an independent numpy statement of the rule to them."""
+    cases = {}
+    ok = (0.0, 0.0, 30.0, 40.0)
+    # -- the prefix: >= thr keeps, the next fp32 below ends it (the 0.9 behind it is never
+    # reached), a NaN score ends it; counts above max_det are clamped to the rows there are
+    thr = 0.25
+    frames = [[(*ok, _above(thr)), (*ok, thr), (*ok, _below(thr)), (*ok, 0.9)],
+              [(*ok, 0.9), (*ok, NAN), (*ok, 0.9)],
+              [(*ok, 0.9), (1.0, 1.0, 31.0, 41.0, 0.8), (2.0, 2.0, 32.0, 42.0, 0.7), (3.0, 3.0, 33.0, 43.0, 0.6)],
+              [(5.0, 5.0, 35.0, 45.0, 0.5)] * 4]
+    d, c = _dets(frames)
+    c[2] = 100                                        # > max_det = 4: frame 3's rows are not frame 2's
+    cases["prefix"] = (d, c, dict(score_thr=thr, max_per_frame=8, max_crops=16), 11, 0,
+                       [(0, 0), (0, 1), (1, 0), (2, 0), (2, 1), (2, 2), (2, 3), (3, 0), (3, 1), (3, 2), (3, 3)])
+    # -- min_size: a side exactly min_size is kept, the next fp32 below is dropped (either side)
+    ms = 4.0
+    frames = [[(10.0, 10.0, 14.0, 50.0, 0.9), (0.0, 10.0, _below(ms), 50.0, 0.8), (10.0, 10.0, 50.0, 14.0, 0.7),
+               (10.0, 0.0, 50.0, _below(ms), 0.6), (10.0, 10.0, 14.0, 14.0, 0.5)]]
+    d, c = _dets(frames)
+    cases["min_size"] = (d, c, dict(min_size=ms, max_crops=8), 3, 0, [(0, 0), (0, 2), (0, 4)])
+    # -- the aspect branch under box_scale_x != box_scale_y: in frame pixels the boxes are
+    # 30 x 40 (w == a h: the else branch, which leaves both sides), 30.75 x 40 (w > a h: h grows)
+    # and 28.5 x 40 (w < a h: w grows); with the scales exchanged all three would be wide
+    frames = [[(10.0, 20.0, 30.0, 100.0, 0.9), (10.0, 20.0, 30.5, 100.0, 0.8), (10.0, 20.0, 29.0, 100.0, 0.7)]]
+    d, c = _dets(frames)
+    cases["aspect"] = (d, c, dict(box_scale=(1.5, 0.5), pad=1.0, max_crops=3), 3, 0, [(0, 0), (0, 1), (0, 2)])
+    # -- +-inf coordinates, and a box that is finite after the scale (w = 2.2e38) whose window
+    # overflows under pad (h = w / a = 2.93e38 is finite, h * 1.25 is inf): both are skipped and
+    # both use up a place among max_per_frame = 3, so row 3 of each frame is never a candidate
+    big = 1.1e38
+    frames = [[(-INF, 0.0, 30.0, 40.0, 0.9), (0.0, 0.0, 30.0, INF, 0.8), ok + (0.7,), ok + (0.6,)],
+              [(-big, 0.0, big, 40.0, 0.9), ok + (0.8,), (0.0, -INF, 30.0, INF, 0.7), ok + (0.6,)]]
+    d, c = _dets(frames)
+    cases["nonfinite"] = (d, c, dict(max_per_frame=3, max_crops=4), 2, 0, [(0, 2), (1, 1)])
+    # -- every slot padded / none padded
+    d, c = _dets([[ok + (0.2,)], [ok + (0.1,)], []])
+    cases["none"] = (d, c, dict(max_crops=5), 0, 0, [])
+    d, c = _dets([[ok + (0.9,), ok + (0.8,)], [], [ok + (0.7,)]])
+    cases["exactly_full"] = (d, c, dict(max_crops=3), 3, 0, [(0, 0), (0, 1), (2, 0)])
+    # -- more frames than threads: counts b % 3 give 255 crops from frames 0..255, so a list of
+    # 400 slots overflows in the second chunk of 256 frames (its last slot is frame 400's only
+    # row: 133 whole cycles of three frames end at frame 398 with 399 crops)
+    B = 600
+    xy = (torch.arange(B * 3 * 2, dtype=torch.float32).view(B, 3, 2) % 37) * 0.5
+    d = torch.cat([xy, xy + 20.0, torch.full((B, 3, 1), 0.5), torch.zeros(B, 3, 1)], 2)
+    c = (torch.arange(B) % 3).int()
+    rows = [(b, r) for b in range(B) for r in range(b % 3)]
+    cases["late_overflow"] = (d, c, dict(max_per_frame=3, max_crops=400), 400, 2, rows[:400])
+    assert rows[399] == (400, 0) and len(rows) == 600
+    # -- counts < 0 at b >= 256 (the second pass of the chunk loop): status bit 0 alone, and
+    # nothing from that frame
+    B = 300
+    d = d[:B, :1].clone()
+    c = torch.ones(B, dtype=torch.int32)
+    c[280] = -1
+    cases["late_negative_count"] = (d, c, dict(max_crops=300), 299, 1, [(b, 0) for b in range(B) if b != 280])
+    return cases
+
+
+def select_plain(dets, counts, score_thr=0.25, max_per_frame=8, min_size=4.0, box_scale=(1.0, 1.0), pad=1.25,
+                 max_crops=8):
+    """include/prpe.h's rule once more, on numpy float32 scalars (each operation rounds once) and
+    with math.isfinite: written apart from ``select_ref`` / ``window_ref`` and sharing no code
+    with them. Returns ([(frame, row, x0, y0, w, h, score)], status)."""
+    import math
+    import numpy as np
+    f = np.float32
+    d = dets.numpy().astype(np.float32)
+    out, status = [], 0
+    with np.errstate(all="ignore"):
+        for b in range(d.shape[0]):
+            c = int(counts[b])
+            if c < 0:
+                status |= 1
+                continue
+            tried = 0
+            for r in range(min(c, d.shape[1])):
+                if tried == max_per_frame or not d[b, r, 4] >= f(score_thr):
+                    break
+                tried += 1
+                x1, x2 = d[b, r, 0] * f(box_scale[0]), d[b, r, 2] * f(box_scale[0])
+                y1, y2 = d[b, r, 1] * f(box_scale[1]), d[b, r, 3] * f(box_scale[1])
+                if not all(math.isfinite(v) for v in (x1, y1, x2, y2)):
+                    continue
+                w, h = f(x2 - x1), f(y2 - y1)
+                if not (w >= f(min_size) and h >= f(min_size)):
+                    continue
+                if w * f(4.0) > h * f(3.0):           # w / h > 3 / 4 (exact for the sizes used here)
+                    h = f(w / f(0.75))
+                else:
+                    w = f(h * f(0.75))
+                w, h = f(w * f(pad)), f(h * f(pad))
+                x0 = f(f(f(x1 + x2) * f(0.5)) - f(f(0.5) * w))
+                y0 = f(f(f(y1 + y2) * f(0.5)) - f(f(0.5) * h))
+                if all(math.isfinite(v) for v in (x0, y0, w, h)):
+                    out.append((b, r, x0, y0, w, h, d[b, r, 4]))
+    if len(out) > max_crops:
+        status |= 2
+    return out[:max_crops], status
+
+
+@pytest.mark.parametrize("name", sorted(select_edge_cases()))
+def test_select_ref_at_the_edges_equals_the_plain_statement(name):
+    """``select_ref`` at the edges the GPU test sends to the kernel, against ``select_plain`` bit
+    for bit and against the literal expectations of ``select_edge_cases``. The rule is this
+    project's own (include/prpe.h): the reference has no crop list, so the header decides --
+    ``>=`` at both thresholds (a NaN compares false and ends the prefix / drops the box), ``>`` in
+    the aspect test, a box or window with a non-finite field skipped after it took its place."""
+    import numpy as np
+    dets, counts, kw, want_n, want_status, want_rows = select_edge_cases()[name]
+    meta, n, status = select_ref(dets, counts, **kw)
+    rows, status_plain = select_plain(dets, counts, **kw)
+    assert (n, status) == (want_n, want_status) == (len(rows), status_plain)
+    assert _frames_rows(meta, n) == want_rows == [(b, r) for b, r, *_ in rows]
+    for s, row in enumerate(rows):
+        assert np.array_equal(meta[s, 2:7].numpy().view(np.int32), np.array(row[2:], np.float32).view(np.int32)), s
+    ints = meta.view(torch.int32)
+    assert bool((ints[n:, 0] == -1).all()) and not bool(ints[n:, 1:].any()) and not bool(ints[:n, 7].any())
+    assert bool(torch.isfinite(meta[:n, 2:7]).all())
+
+
+def test_window_ref_at_the_aspect_equality_and_under_unequal_scales():
+    """The windows of the ``aspect`` case by hand: 30 x 40 stays (w == a h takes the else branch,
+    w = h a = 30), 30.75 x 40 grows to 30.75 x 41, 28.5 x 40 grows to 30 x 40 about its own
+    centre."""
+    dets, counts, kw, *_ = select_edge_cases()["aspect"]
+    meta, n, _ = select_ref(dets, counts, **kw)
+    assert [float(v) for v in meta[0, 2:6]] == [15.0, 10.0, 30.0, 40.0]
+    assert [float(v) for v in meta[1, 2:6]] == [15.0, 9.5, 30.75, 41.0]
+    assert [float(v) for v in meta[2, 2:6]] == [14.25, 10.0, 30.0, 40.0]
+
+
 # ---------------------------------------------------------------------------------- host helpers
 def test_results_formatting():
     from prpe import TopDownPose
