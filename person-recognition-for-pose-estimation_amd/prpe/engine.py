@@ -93,6 +93,27 @@ PATCH_VIEW = os.environ.get("PRPE_VIT_PATCH_VIEW", "1") != "0"
 T1_BORDER = os.environ.get("PRPE_T1_BORDER", "1") != "0"
 
 
+class Act:
+    """An activation as one layer hands it to the next: the device tensor (logical NHWC view) and
+    what the engine knows about it. A view of ``t`` is a new tensor with none of this: where the
+    metadata holds for the view too, the code builds a new Act there and says why."""
+    __slots__ = ("t", "amax", "planes", "pooled", "epoch", "pix4")
+
+    def __init__(self, t, amax=None, planes=False, pooled=False, epoch=None, pix4=None):
+        self.t = t              # the device tensor
+        self.amax = amax        # [N] device slots bounding max|t[n]| (precision 3/4 operand scale), or None
+        self.planes = planes    # t holds bf16 hi/lo planes (include/prpe.h), not fp32
+        self.pooled = pooled    # the stem launch already max-pooled
+        self.epoch = epoch      # (component, n): amax is valid while the component's pool epoch is n
+        self.pix4 = pix4        # the zero-bordered NHWC4 buffer t is the interior of, or None
+
+
+def _act(x) -> Act:
+    """``x`` as an Act: a bare tensor (frames, pixel_values, a slice of a concat buffer) carries no
+    metadata."""
+    return x if isinstance(x, Act) else Act(x)
+
+
 class _Prec:
     """Component scope: its precision from the policy and, at precision 3, its own max|y| slot
     pool (zeroed on entry, on the current stream)."""
@@ -244,9 +265,8 @@ class Engine:
         """``prologue``: an input-side affine is allowed (precision 4 bounds it in-kernel)."""
         chunked = p.k_order == 1 or (p.kh * p.kw == 1 and p.ci % 32 == 0)
         # (a planes-format input is read by precision 0 only: its consumer drops to 0 as well)
-        return (chunked and (prologue or p.in_scale is None) and x.stride(3) == 1 and x.data_ptr() % 16 == 0 and
-                Engine._vec4(out) and Engine._vec4(res) and getattr(x, "_prpe_amax", None) is not None and
-                not getattr(x, "_prpe_planes", False))
+        return (chunked and (prologue or p.in_scale is None) and x.t.stride(3) == 1 and x.t.data_ptr() % 16 == 0 and
+                Engine._vec4(out) and Engine._vec4(res) and x.amax is not None and not x.planes)
 
     def pk_dual(self, q) -> ConvPack:
         """Bottleneck ``q`` (block 0 of a stage): relu(bn3(conv3(o)) + bn_ds(downsample(x))) as
@@ -265,42 +285,42 @@ class Engine:
             self._packs[name] = p
         return p
 
-    def conv(self, x, p: ConvPack, out=None, res=None, res_mode=0, act=None, x2=None, x2_amax=None,
-             planes_out=False, w2=None, y2=None, prec=None, track=True, **stage2):
-        """``x2``: second 1x1 input on the output grid (dual-input GEMM, see prpe.h).
+    def conv(self, x, p: ConvPack, out=None, res=None, res_mode=0, act=None, x2=None, planes_out=False, w2=None,
+             y2=None, prec=None, track=True, **stage2):
+        """``x``, ``res``: an Act or a bare tensor. ``out``: the caller's view to write (a tensor,
+        or an Act, which is then the one returned). Returns the output as an Act.
+        ``x2``: second 1x1 input on the output grid, an Act (dual-input GEMM, see prpe.h).
         ``planes_out``: the only consumer is a precision-0 wave-row conv: write the planes format.
         ``w2``/``y2``: epilogue 1x1 GEMM into y2 (prpe.h); ``out`` is then not written;
         ``stage2``: its second stage (w3, scale2, bias2, act2; prpe.h).
         ``prec``: this conv's precision instead of the component's (Engine.feat_prec).
         ``track``: raise the output's per-frame max|y| slots in a precision-3/4 component (off for
         an output no conv consumes, e.g. the IR-50 output layer's split-K GEMM)."""
-        B, H, W, _ = x.shape
+        x, res = _act(x), res.t if isinstance(res, Act) else res
+        B, H, W, _ = x.t.shape
         Ho = (H + 2 * p.pad - p.kh) // p.stride + 1
         Wo = (W + 2 * p.pad - p.kw) // p.stride + 1
-        if out is None:
-            out = self.empty(B, Ho, Wo, p.co)
+        out = _act(self.empty(B, Ho, Wo, p.co) if out is None else out)
         prec = self.precision if prec is None else prec
-        if prec == 3 and (not self._f16_ok(x, p, out, res) or (x2 is not None and x2_amax is None)):
+        if prec == 3 and (not self._f16_ok(x, p, out.t, res) or (x2 is not None and x2.amax is None)):
             prec = 2
-        if prec == 4 and (not self._f16_ok(x, p, out, res, prologue=True) or x2 is not None):
+        if prec == 4 and (not self._f16_ok(x, p, out.t, res, prologue=True) or x2 is not None):
             prec = 0
-        xa = getattr(x, "_prpe_amax", None) if prec in F16_PRECS else None
+        xa = x.amax if prec in F16_PRECS else None
         ya = self.amax_slot(B) if self.precision in F16_PRECS and w2 is None and track else None
-        x_planes = getattr(x, "_prpe_planes", False)
-        if x_planes and prec != 0:
+        if x.planes and prec != 0:
             raise RuntimeError(f"{p.name}: planes-format input needs precision 0, got {prec}")
         # planes output only where the component itself runs precision 0 (as upconv(): inside a
         # precision-3/4 scope a conv that fell back to 0 keeps fp32 output for its f16 consumers)
         y_planes = (PLANES_ON and planes_out and prec == 0 and self.precision == 0 and p.co % 8 == 0 and
-                    out.is_contiguous())
-        kw = dict(res=res, res_mode=res_mode, act=act, precision=prec, tile=p.tile, x_amax=xa, y_amax=ya, x2=x2,
-                  x2_amax=x2_amax if prec == 3 else None, x_planes=x_planes, y_planes=y_planes, w2=w2, y2=y2,
-                  **stage2)
-        self._timed(p.name, self.events, p.name, (B * Ho * Wo, p, prec, x.numel()),
-                    lambda: ops.conv2d(x, p, out, **kw))
-        out._prpe_amax = ya
-        if y_planes:
-            out._prpe_planes = True
+                    out.t.is_contiguous())
+        kw = dict(res=res, res_mode=res_mode, act=act, precision=prec, tile=p.tile, x_amax=xa, y_amax=ya,
+                  x_planes=x.planes, y_planes=y_planes, w2=w2, y2=y2, **stage2)
+        if x2 is not None:
+            kw.update(x2=x2.t, x2_amax=x2.amax if prec == 3 else None)
+        self._timed(p.name, self.events, p.name, (B * Ho * Wo, p, prec, x.t.numel()),
+                    lambda: ops.conv2d(x.t, p, out.t, **kw))
+        out.amax, out.planes = ya, y_planes
         return out
 
     def upconv(self, name, x, wkey, size, align_corners, bn=None, bias_key=None, act="none", prelu=None, out=None,
@@ -308,7 +328,8 @@ class Engine:
         """conv3x3(pad 1)(bilinear_upsample(x, size)) [+BN] [+act] via the tap rewrite.
         ``planes``: the only consumer is a precision-0 conv, so write the planes format (the
         consumer's two-plane split done once here; include/prpe.h).
-        ``z``: the tap GEMM's output, already computed (``x`` is then unused)."""
+        ``z``: the tap GEMM's output (a tensor), already computed (``x`` is then unused).
+        ``out``: as ``conv``'s."""
         taps = self._packs.get(name + ":taps")
         if taps is None:
             taps = pack_upconv_taps(name + ":taps", self.sd[wkey], self.device)
@@ -324,20 +345,17 @@ class Engine:
             self._aux[key] = s.float().to(self.device)
             self._aux[key + "b"] = b.float().contiguous().to(self.device)
         if z is None:
-            z = self.conv(x, taps)
+            z = self.conv(x, taps).t
         B = z.shape[0]
-        if out is None:
-            out = self.empty(B, size[0], size[1], co)
+        out = _act(self.empty(B, size[0], size[1], co) if out is None else out)
         slope = self.dev(prelu) if prelu else None
-        planes = PLANES_ON and planes and self.precision == 0 and co % 8 == 0 and out.is_contiguous()
+        planes = PLANES_ON and planes and self.precision == 0 and co % 8 == 0 and out.t.is_contiguous()
         # a precision-3/4 consumer reads the output's per-frame max|y| as its activation scale
         ya = self.amax_slot(B) if self.precision in F16_PRECS else None
-        args = (z, out, align_corners, self._aux[key], self._aux[key + "b"], slope, act)
-        self._timed(name + ":upconv", self.up_events, name, (out.numel() * 4, z.numel() * 4, planes, act),
+        args = (z, out.t, align_corners, self._aux[key], self._aux[key + "b"], slope, act)
+        self._timed(name + ":upconv", self.up_events, name, (out.t.numel() * 4, z.numel() * 4, planes, act),
                     lambda: ops.upconv3x3(*args, y_planes=planes, y_amax=ya))
-        out._prpe_amax = ya
-        if planes:
-            out._prpe_planes = True
+        out.amax, out.planes = ya, planes
         return out
 
     def conv3x3_smallco(self, x, name, wkey, bn=None, bias_key=None, act="none", out=None):
@@ -348,8 +366,7 @@ class Engine:
         unit scale: every source index is exact, interpolation weights 1 and 0). Same
         function as the conv; fp32 summation order differs."""
         if SMALLCO_TAPS:
-            return self.upconv(name, x, wkey, (x.shape[1], x.shape[2]), True, bn=bn, bias_key=bias_key, act=act,
-                               out=out)
+            return self.upconv(name, x, wkey, x.t.shape[1:3], True, bn=bn, bias_key=bias_key, act=act, out=out)
         return self.conv(x, self.pk(name, wkey, 1, 1, bn=bn, bias_key=bias_key, act=act), out=out)
 
     # ------------------------------------------------------------------ ResNet-50 trunk
@@ -358,7 +375,7 @@ class Engine:
         ``flip_w``: run on the W-mirrored frames (torch.flip(images, dims=[-1]))."""
         with self.prec("trunk"):
             y = self._trunk(x_nchw, flip_w)
-            y._prpe_amax_tag = ("trunk", self._amax_epoch.get("trunk"))
+            y.epoch = ("trunk", self._amax_epoch.get("trunk"))
             return y
 
     def feat_prec(self, feat):
@@ -367,8 +384,9 @@ class Engine:
         call wrote (the trunk pool is re-zeroed by the next trunk call), else the head's own.
         Measured: the face-YOLO adapter's 2048-deep .0 GEMM at precision 0 carried most of the
         box-coordinate error of policy "auto" (tools/yolo_adapter_prec_diag.py)."""
-        tag = getattr(feat, "_prpe_amax_tag", None)
-        if tag is not None and getattr(feat, "_prpe_amax", None) is not None and \
+        feat = _act(feat)
+        tag = feat.epoch
+        if tag is not None and feat.amax is not None and \
                 self._amax_epoch.get(tag[0]) == tag[1] and self.policy.get("trunk") == 3:
             return 3
         return None
@@ -405,8 +423,8 @@ class Engine:
     def _stem_conv(self, buf, amax, H0, W0, pool):
         """What follows the fill of the stem buffer: the strided view, the pack, the conv (+ pool)."""
         B0 = buf.shape[0]
-        v = buf.as_strided((B0, H0 + 6, W0, 32), (buf.stride(0), buf.stride(1), 4, 1))
-        v._prpe_amax = amax
+        # the overlapping view holds the buffer's values and no others: the fill's slots bound it
+        v = Act(buf.as_strided((B0, H0 + 6, W0, 32), (buf.stride(0), buf.stride(1), 4, 1)), amax)
         stem = self._packs.get("backbone.conv1")
         if stem is None:
             w = self.sd["backbone.conv1.weight"].float()             # [64, 3, 7, 7]
@@ -424,9 +442,7 @@ class Engine:
             name = "backbone.conv1+maxpool"
             self._timed(name, self.events, name, (B0 * (H0 // 2) * (W0 // 2), stem, 3, buf.numel()),
                         lambda: ops.stem_maxpool(buf, H0, W0, amax, stem, y, ya))
-            y._prpe_amax = ya
-            y._prpe_pooled = True
-            return y
+            return Act(y, ya, pooled=True)
         return self.conv(v, stem)
 
     def trunk_u8(self, frames_u8, ingest):
@@ -434,20 +450,19 @@ class Engine:
         stem conv on, so the same bits as ``trunk`` on fp32 frames holding what the ingest wrote."""
         with self.prec("trunk"):
             y = self._trunk_layers(self.stem_u8(frames_u8, ingest, pool=True))
-            y._prpe_amax_tag = ("trunk", self._amax_epoch.get("trunk"))
+            y.epoch = ("trunk", self._amax_epoch.get("trunk"))
             return y
 
     def _trunk(self, x_nchw, flip_w=False):
         return self._trunk_layers(self.stem(x_nchw, flip_w, pool=True))
 
     def _trunk_layers(self, y):
-        if getattr(y, "_prpe_pooled", False):
+        if y.pooled:
             x = y
         else:
-            B, H, W, C = y.shape
+            B, H, W, C = y.t.shape
             mp = self.empty(B, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, C)
-            x = ops.maxpool(y, mp, 3, 2, 1)
-            x._prpe_amax = y._prpe_amax    # max-pooling never raises max|x|
+            x = Act(ops.maxpool(y.t, mp, 3, 2, 1), y.amax)    # max-pooling never raises max|x|
         for li, (planes, blocks, stride) in enumerate(arch.RESNET50_STAGES, 1):
             for b in range(blocks):
                 q = f"backbone.layer{li}.{b}"
@@ -464,10 +479,10 @@ class Engine:
                     # all of it unpadded (pad 0): same sums (a padded tap adds 0 either way), and
                     # the conv has no tap masks, so it takes conv_wave's pixel-contiguous A loads
                     # (XM 2; csrc/conv_wave.hip)
-                    B_, H_, W_, _ = x.shape
+                    B_, H_, W_, _ = x.t.shape
                     tb = self.bordered(B_, H_, W_, p1.co)
                     o = self.conv(x, p1, out=tb[:, 1:H_ + 1, 1:W_ + 1, :])
-                    tb._prpe_amax = o._prpe_amax                  # the zero border never raises max|x|
+                    tb = Act(tb, o.amax)                          # the zero border never raises max|x|
                     o = self.conv(tb, self.pk(q + ".conv2", q + ".conv2.weight", s, 0, bn=q + ".bn2", act="relu"))
                 else:
                     o = self.conv(x, p1)
@@ -475,8 +490,8 @@ class Engine:
                 if b == 0:
                     # conv3 + bn3 and the downsample projection + its BN summed in one dual-input
                     # GEMM: the projection never goes to HBM as a residual tensor
-                    xs = x if s == 1 else x[:, ::s, ::s, :]
-                    x = self.conv(o, self.pk_dual(q), x2=xs, x2_amax=getattr(x, "_prpe_amax", None))
+                    xs = x if s == 1 else Act(x.t[:, ::s, ::s, :], x.amax)    # a subsample never raises max|x|
+                    x = self.conv(o, self.pk_dual(q), x2=xs)
                 else:
                     x = self.conv(o, self.pk(q + ".conv3", q + ".conv3.weight", bn=q + ".bn3", act="relu"),
                                   res=x, res_mode=RES_PRE)
@@ -485,8 +500,8 @@ class Engine:
     def _bneck_ok(self, x, planes, proj=False):
         return (BNECK_FUSE and (BNECK_PROJ or not proj) and self.precision == 3 and
                 (planes == 64 or (planes == 128 and BNECK_L2 and not proj)) and
-                x.shape[3] == (planes if proj else 4 * planes) and
-                x.is_contiguous() and getattr(x, "_prpe_amax", None) is not None)
+                x.t.shape[3] == (planes if proj else 4 * planes) and
+                x.t.is_contiguous() and x.amax is not None)
 
     def bottleneck(self, q, x, proj=False):
         """Bottleneck ``q`` (torchvision Bottleneck.forward) as one fused launch (prpe_bottleneck);
@@ -496,12 +511,12 @@ class Engine:
                  self.pk(q + ".conv2", q + ".conv2.weight", 1, 1, bn=q + ".bn2", act="relu"),
                  self.pk_dual(q) if proj else
                  self.pk(q + ".conv3", q + ".conv3.weight", bn=q + ".bn3", act="relu"))
-        y = self.empty(*x.shape[:3], packs[2].co)
-        ya = self.amax_slot(x.shape[0])
-        self._timed(q, self.events, q, (x.shape[0] * x.shape[1] * x.shape[2], packs[1], 3, x.numel()),
-                    lambda: ops.bottleneck(x, packs, y, x._prpe_amax, ya))
-        y._prpe_amax = ya
-        return y
+        B, H, W, _ = x.t.shape
+        y = self.empty(B, H, W, packs[2].co)
+        ya = self.amax_slot(B)
+        self._timed(q, self.events, q, (B * H * W, packs[1], 3, x.t.numel()),
+                    lambda: ops.bottleneck(x.t, packs, y, x.amax, ya))
+        return Act(y, ya)
 
     # ------------------------------------------------------------------ YOLO v11n branch
     def yc(self, q, x, k, s=1, act="silu", out=None, res=None, res_mode=0):
@@ -517,16 +532,17 @@ class Engine:
             self._aux[key] = self.sd[q + ".conv.weight"].float().reshape(-1).contiguous().to(self.device)
             self._aux[key + "s"] = s.to(self.device)
             self._aux[key + "b"] = b.to(self.device)
+        x = _act(x).t
         if out is None:
             out = self.empty(*x.shape)
-        return ops.dwconv(x, out, self._aux[key], 3, 1, 1, self._aux[key + "s"], self._aux[key + "b"], act, res)
+        return Act(ops.dwconv(x, out, self._aux[key], 3, 1, 1, self._aux[key + "s"], self._aux[key + "b"], act, res))
 
     def residual(self, q, x, out=None):                       # nn.py:42-49
         t = self.yc(q + ".conv1", x, 3)
         return self.yc(q + ".conv2", t, 3, out=out, res=x, res_mode=RES_POST)
 
     def cspmodule(self, q, x, out=None):                      # nn.py:52-63
-        B, H, W, c = x.shape
+        B, H, W, c = _act(x).t.shape
         Z = self.empty(B, H, W, c)
         h = c // 2
         a = self.yc(q + ".conv1", x, 1)
@@ -536,7 +552,7 @@ class Engine:
         return self.yc(q + ".conv3", Z, 1, out=out)
 
     def csp(self, q, x, cout, csp, r, out=None):              # nn.py:66-80 (n = 1)
-        B, H, W, _ = x.shape
+        B, H, W, _ = _act(x).t.shape
         c = cout // r
         Y = self.empty(B, H, W, 3 * c)
         self.yc(q + ".conv1", x, 1, out=Y[..., :2 * c])
@@ -547,7 +563,7 @@ class Engine:
         return self.yc(q + ".conv2", Y, 1, out=out)
 
     def spp(self, q, x):                                      # nn.py:83-94
-        B, H, W, c = x.shape
+        B, H, W, c = _act(x).t.shape
         S = self.empty(B, H, W, 2 * c)
         h = c // 2
         self.yc(q + ".conv1", x, 1, out=S[..., :h])
@@ -556,22 +572,22 @@ class Engine:
         return self.yc(q + ".conv2", S, 1)
 
     def psa(self, q, x, out=None):                            # nn.py:97-148
-        B, H, W, ch = x.shape
+        B, H, W, ch = _act(x).t.shape
         T = self.yc(q + ".conv1", x, 1)
         c = ch // 2
         nh = ch // 128
         dh = c // nh
         dk = dh // 2
-        y = T[..., c:]
+        y = T.t[..., c:]
         blk = q + ".res_m.0"
         qkv = self.yc(blk + ".conv1.qkv", y, 1, act="none")
         A = self.empty(B, H, W, c)
         V = self.empty(B, H, W, c)
-        ops.psa_attention(qkv, A, V, nh, dk, dh, dk ** -0.5)
+        ops.psa_attention(qkv.t, A, V, nh, dk, dh, dk ** -0.5)
         D = self.ydw(blk + ".conv1.conv1", V, act="none", res=A)            # attn + dwconv(v)
         Y1 = self.yc(blk + ".conv1.conv2", D, 1, act="none", res=y, res_mode=RES_POST)
         Hh = self.yc(blk + ".conv2.0", Y1, 1)
-        self.yc(blk + ".conv2.1", Hh, 1, act="none", res=Y1, res_mode=RES_POST, out=T[..., c:])
+        self.yc(blk + ".conv2.1", Hh, 1, act="none", res=Y1, res_mode=RES_POST, out=T.t[..., c:])
         return self.yc(q + ".conv2", T, 1, out=out)
 
     def yolo(self, p, feat, stride=(0.0, 0.0, 0.0)):
@@ -597,7 +613,7 @@ class Engine:
                         act="silu", planes=True)
         t = self.conv(u, p7, planes_out=True)
         p10 = self.pk(a + ".10", a + ".10.weight", 1, 1, bn=a + ".11", bias_key=a + ".10.bias", act="silu")
-        if SMALLCO_TAPS and TAPS_FUSE and getattr(t, "_prpe_planes", False):
+        if SMALLCO_TAPS and TAPS_FUSE and t.planes:
             # .10's epilogue runs .13 (1x1 128->64 + BN + SiLU) and .16's tap GEMM (64 -> 27):
             # neither the 128- nor the 64-channel map reaches HBM (prpe.h, w2 / w3)
             w2 = self.dev(a + ".13:w", lambda: self.sd[a + ".13.weight"].float().flatten(1))
@@ -605,13 +621,13 @@ class Engine:
             b2 = self.dev(a + ".13:b", lambda: bn_affine(self.sd, a + ".14", BN_EPS, self.sd[a + ".13.bias"])[1])
             w3 = self.dev(a + ".16:w2", lambda: self.sd[a + ".16.weight"].float().permute(2, 3, 0, 1)
                           .reshape(-1, w2.shape[0]).contiguous())
-            B, H, W, _ = t.shape
+            B, H, W, _ = t.t.shape
             z = self.empty(B, H, W, w3.shape[0])
             sink = self.dev("sink:" + str(p10.co), lambda: torch.zeros(p10.co)).expand(B, H, W, p10.co)
             self.conv(t, p10, out=sink, w2=w2, y2=z, w3=w3, scale2=s2, bias2=b2, act2="silu")
             t = self.upconv(a + ".16", None, a + ".16.weight", (H, W), True, bn=a + ".17", bias_key=a + ".16.bias",
                             act="silu", z=z)
-            return ops.norm_sigmoid(t, self.empty(*t.shape))
+            return Act(ops.norm_sigmoid(t.t, self.empty(*t.t.shape)))
         # .10 and .13 write fp32: the 64-column 1x1 below runs faster on the register-staged
         # 256x64 tile than on the planes-input wave tile (1.12 vs 1.64 ms at bs=256), and the
         # 27-column tap GEMM after .13 needs fp32 input
@@ -619,31 +635,31 @@ class Engine:
         t = self.conv(t, self.pk(a + ".13", a + ".13.weight", bn=a + ".14", bias_key=a + ".13.bias", act="silu"))
         t = self.conv3x3_smallco(t, a + ".16", a + ".16.weight", bn=a + ".17", bias_key=a + ".16.bias",
                                  act="silu")
-        return ops.norm_sigmoid(t, self.empty(*t.shape))
+        return Act(ops.norm_sigmoid(t.t, self.empty(*t.t.shape)))
 
     def yolo_net(self, p, s, stride):
-        B = s.shape[0]
+        B = _act(s).t.shape[0]
         n = p + ".yolo.net"
         x = self.yc(n + ".p1.0", s, 3, 2)
         x = self.csp(n + ".p2.1", self.yc(n + ".p2.0", x, 3, 2), 64, False, 4)
         x = self.yc(n + ".p3.0", x, 3, 2)
-        _, H3, W3, _ = x.shape
+        _, H3, W3, _ = x.t.shape
         F2 = self.empty(B, H3, W3, 256)                     # cat(up(h1), p3)
         p3 = self.csp(n + ".p3.1", x, 128, False, 4, out=F2[..., 128:])
         x = self.yc(n + ".p4.0", p3, 3, 2)
-        _, H4, W4, _ = x.shape
+        _, H4, W4, _ = x.t.shape
         F1 = self.empty(B, H4, W4, 384)                     # cat(up(p5), p4)
         p4 = self.csp(n + ".p4.1", x, 128, True, 2, out=F1[..., 256:])
         x = self.csp(n + ".p5.1", self.yc(n + ".p5.0", p4, 3, 2), 256, True, 2)
         x = self.spp(n + ".p5.2", x)
-        _, H5, W5, _ = x.shape
+        _, H5, W5, _ = x.t.shape
         F4 = self.empty(B, H5, W5, 384)                     # cat(h5(p4''), p5)
         p5 = self.psa(n + ".p5.3", x, out=F4[..., 128:])
         f = p + ".yolo.fpn"
-        ops.upsample_nearest2x(p5, F1[..., :256])
+        ops.upsample_nearest2x(p5.t, F1[..., :256])
         F3 = self.empty(B, H4, W4, 192)                     # cat(h3(p3'), p4')
         h1 = self.csp(f + ".h1", F1, 128, False, 2, out=F3[..., 64:])
-        ops.upsample_nearest2x(h1, F2[..., :128])
+        ops.upsample_nearest2x(h1.t, F2[..., :128])
         P3 = self.csp(f + ".h2", F2, 64, False, 2)
         self.yc(f + ".h3", P3, 3, 2, out=F3[..., :64])
         P4 = self.csp(f + ".h4", F3, 128, False, 2)
@@ -653,13 +669,13 @@ class Engine:
 
     def head(self, h, feats, stride):
         """Head eval (nn.py:255-270): box/cls convs per level -> one [B, A, 65] buffer -> DFL decode."""
-        B = feats[0].shape[0]
-        A = sum(x.shape[1] * x.shape[2] for x in feats)
+        B = feats[0].t.shape[0]
+        A = sum(x.t.shape[1] * x.t.shape[2] for x in feats)
         HEAD = self.empty(B, A, 65)
         off = 0
         hw = []
         for i, x in enumerate(feats):
-            _, H, W, _ = x.shape
+            _, H, W, _ = x.t.shape
             hv = HEAD[:, off:off + H * W, :].view(B, H, W, 65)
             t = self.yc(f"{h}.box.{i}.1", self.yc(f"{h}.box.{i}.0", x, 3), 3)
             self.conv(t, self.pk(f"{h}.box.{i}.2", f"{h}.box.{i}.2.weight", bias_key=f"{h}.box.{i}.2.bias"),
@@ -697,7 +713,7 @@ class Engine:
         for i, (cin, d, st) in enumerate(arch.IR50_UNITS):
             q = f"{m}.body.{i}"
             if cin == d:
-                sc = x[:, ::st, ::st, :]                      # MaxPool2d(1, st) == subsample
+                sc = x.t[:, ::st, ::st, :]                    # MaxPool2d(1, st) == subsample
             else:
                 sc = self.conv(x, self.pk(q + ".shortcut", q + ".shortcut_layer.0.weight", st, 0,
                                           bn=q + ".shortcut_layer.1"))
@@ -721,8 +737,8 @@ class Engine:
                             k_order=0 if tile == 0 else "auto")
             lin.tile = tile
             self._packs["ir50.output"] = lin
-        B = x.shape[0]
-        y = self.conv(x, lin, prec=0, track=False)           # [B,1,1,512]
+        B = x.t.shape[0]
+        y = self.conv(x, lin, prec=0, track=False).t         # [B,1,1,512]
         emb = self.empty(B, 512)
         norm = self.empty(B, 1)
         ops.l2norm(y.view(B, 512), emb, norm)
@@ -737,12 +753,12 @@ class Engine:
         u = self.upconv(a + ".4", t, a + ".4.weight", arch.VIT_IMG, True, bn=a + ".5", bias_key=a + ".4.bias",
                         act="gelu", planes=True)
         p7 = self.pk(a + ".7", a + ".7.weight", 1, 1, bn=a + ".8", bias_key=a + ".7.bias", act="gelu")
-        if SMALLCO_TAPS and TAPS_FUSE and getattr(u, "_prpe_planes", False):
+        if SMALLCO_TAPS and TAPS_FUSE and u.planes:
             # .7's epilogue computes .10's tap GEMM (w2 = .10's weight as [(tap, co), ci], the
             # pack_upconv_taps order); its 128-channel output exists only in LDS
             w2 = self.dev(a + ".10:w2", lambda: self.sd[a + ".10.weight"].float().permute(2, 3, 0, 1)
                           .reshape(-1, p7.co).contiguous())
-            B, H, W, _ = u.shape
+            B, H, W, _ = u.t.shape
             z = self.empty(B, H, W, w2.shape[0])
             sink = self.dev("sink:" + str(p7.co), lambda: torch.zeros(p7.co)).expand(B, H, W, p7.co)
             self.conv(u, p7, out=sink, w2=w2, y2=z)
@@ -751,7 +767,7 @@ class Engine:
                                bias_key=a + ".10.bias", act="gelu", z=z, out=out)
         t = self.conv(u, p7)
         return self.conv3x3_smallco(t, a + ".10", a + ".10.weight", bn=a + ".11", bias_key=a + ".10.bias",
-                                    act="gelu", out=self._vit_pix_out(t.shape[0]))
+                                    act="gelu", out=self._vit_pix_out(t.t.shape[0]))
 
     # ---- the ViTPose crops in a zero-bordered NHWC4 buffer [B, 256+4, 192+4, 4] (2 rows / columns
     # of padding = the patch conv's pad, the 4th channel 0): the adapter's last conv writes the
@@ -761,13 +777,7 @@ class Engine:
         return self._batch_buf("vit_pix4", B, (H + 4, W + 4, 4))
 
     def _vit_pix_out(self, B):
-        if not PATCH_VIEW:
-            return None
-        H, W = arch.VIT_IMG
-        buf = self.vit_pix4(B)
-        out = buf[:, 2:2 + H, 2:2 + W, :3]
-        out._prpe_pix4 = buf
-        return out
+        return self.pix4_interior(self.vit_pix4(B)) if PATCH_VIEW else None
 
     def crop_pix4(self, n):
         """The top-down crops (prpe.topdown): the zero-bordered NHWC4 buffer [n, 260, 196, 4]
@@ -779,12 +789,11 @@ class Engine:
 
     @staticmethod
     def pix4_interior(buf):
-        """The pixel_values view [n, 256, 192, 3] of a pix4 buffer (or of its first n slots),
-        tagged so that vit_backbone reads the buffer in place instead of copying into vit_pix4."""
+        """The pixel_values view [n, 256, 192, 3] of a pix4 buffer (or of its first n slots) as an
+        Act that names the buffer, so that vit_backbone reads it in place instead of copying into
+        vit_pix4."""
         H, W = arch.VIT_IMG
-        pix = buf[:, 2:2 + H, 2:2 + W, :3]
-        pix._prpe_pix4 = buf
-        return pix
+        return Act(buf[:, 2:2 + H, 2:2 + W, :3], pix4=buf)
 
     def _lin(self, name, wkey, bkey, act="none"):
         p = self._packs.get(name)
@@ -798,7 +807,8 @@ class Engine:
     def vit_backbone(self, pix):
         """VitPoseForPoseEstimation.forward (modeling_vitpose.py:190-278) -> heatmaps [B,17,64,48]."""
         v = "vit_pose.vit_pose.backbone"
-        B = pix.shape[0]
+        pix = _act(pix)
+        B = pix.t.shape[0]
         Hp, Wp = arch.VIT_GRID
         L, D = Hp * Wp, arch.VIT_HIDDEN
         pos = self.dev("vit.possum", lambda: (self.sd[v + ".embeddings.position_embeddings"][0, 1:] +
@@ -810,10 +820,10 @@ class Engine:
             # V[b, h, w, 0:64] = P4[b, h, w : w+16, 0:4] (pixel stride 4 floats), P4 the zero-bordered
             # NHWC4 crops (the padding is the conv's); W'[co][kw*4 + c][kh] = W[co, c, kh, kw] (0 for
             # c = 3). One contiguous 256-B row segment per tap row: the chunked implicit GEMM
-            P4 = getattr(pix, "_prpe_pix4", None)
+            P4 = pix.pix4
             if P4 is None:                             # pixel_values from the caller (config 3)
                 P4 = self.vit_pix4(B)
-                ops.copy_pad(pix, P4[:, 2:2 + pix.shape[1], 2:2 + pix.shape[2], :])
+                ops.copy_pad(pix.t, P4[:, 2:2 + pix.t.shape[1], 2:2 + pix.t.shape[2], :])
             Hv, Wv = P4.shape[1], (Wp - 1) * arch.VIT_PATCH + 1
             V = P4.as_strided((B, Hv, Wv, 64), (P4.stride(0), P4.stride(1), 4, 1))
             patch = self._packs.get("vit.patch4")
@@ -833,11 +843,8 @@ class Engine:
         X2 = X.view(B * L, D)
         as4 = lambda t: t.view(t.shape[0], 1, 1, t.shape[1])
 
-        def as4p(t):
-            # the producer wrote the planes format: the GEMM consumer reads it without a split
-            t4 = as4(t)
-            t4._prpe_planes = pl
-            return t4
+        # the producer wrote the planes format, which a reshape keeps: the GEMM consumer reads it without a split
+        as4p = lambda t: Act(as4(t), planes=pl)
         # LayerNorm and attention write their outputs in the planes format when precision 0
         # consumes them (qkv / fc1 / proj GEMMs: the operand split done once by the producer)
         pl = PLANES_ON and self.precision == 0
@@ -849,17 +856,17 @@ class Engine:
                                self.dev(q + ".layernorm_before.bias"), planes=pl)
             qkv = self.conv(as4p(hn), self._lin(q + ":qkv", [A + ".query.weight", A + ".key.weight", A + ".value.weight"],
                                                 [A + ".query.bias", A + ".key.bias", A + ".value.bias"]))
-            ctx = ops.attention_strided(qkv, (L * 3 * D, D, Dh, 3 * D), self.empty(B * L, D), B, L, Hh, Dh,
+            ctx = ops.attention_strided(qkv.t, (L * 3 * D, D, Dh, 3 * D), self.empty(B * L, D), B, L, Hh, Dh,
                                         Dh ** -0.5, out_planes=pl)
             X2 = self.conv(as4p(ctx), self._lin(q + ":proj", q + ".attention.output.dense.weight",
                                                 q + ".attention.output.dense.bias"),
-                           res=as4(X2), res_mode=RES_PRE).view(B * L, D)
+                           res=as4(X2), res_mode=RES_PRE).t.view(B * L, D)
             hn = ops.layernorm(X2, self.empty(B * L, D), self.dev(q + ".layernorm_after.weight"),
                                self.dev(q + ".layernorm_after.bias"), planes=pl)
             f1 = self.conv(as4p(hn), self._lin(q + ":fc1", q + ".mlp.fc1.weight", q + ".mlp.fc1.bias", act="gelu"),
                            planes_out=True)
             X2 = self.conv(f1, self._lin(q + ":fc2", q + ".mlp.fc2.weight", q + ".mlp.fc2.bias"),
-                           res=as4(X2), res_mode=RES_PRE).view(B * L, D)
+                           res=as4(X2), res_mode=RES_PRE).t.view(B * L, D)
         hn = ops.layernorm(X2, self.empty(B * L, D), self.dev(v + ".layernorm.weight"), self.dev(v + ".layernorm.bias"),
                            relu=True)
         heat = self.empty(B, arch.NUM_KEYPOINTS, *arch.HEATMAP)

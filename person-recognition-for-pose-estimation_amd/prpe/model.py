@@ -238,14 +238,15 @@ class CombinedModel:
         if not concurrent:
             det, (emb, norm), heat = (h() for h in heads)
             return {"det": det, "emb": emb, "norm": norm, "heatmaps": heat}
-        main = torch.cuda.current_stream(feat.device)
-        if getattr(self, "_head_streams", None) is None or self._head_streams[0].device != feat.device:
-            self._head_streams = [torch.cuda.Stream(feat.device) for _ in heads]
+        dev = feat.t.device                  # feat: the trunk's engine.Act
+        main = torch.cuda.current_stream(dev)
+        if getattr(self, "_head_streams", None) is None or self._head_streams[0].device != dev:
+            self._head_streams = [torch.cuda.Stream(dev) for _ in heads]
         fork = main.record_event()
         outs = []
         for s, h in zip(self._head_streams, heads):
             s.wait_event(fork)
-            feat.record_stream(s)            # feat is freed on `main`; keep it alive for `s`
+            feat.t.record_stream(s)          # feat is freed on `main`; keep it alive for `s`
             with torch.cuda.stream(s):
                 outs.append(h())
         for s in self._head_streams:

@@ -20,17 +20,17 @@ def eng(state_dict):
 def _both(eng, x, flip=False):
     with eng.prec("trunk"):
         yf = eng.stem(x, flip, pool=True)
-        assert getattr(yf, "_prpe_pooled", False)
-        fa = yf._prpe_amax.clone()
-        yf = yf.clone()
+        assert yf.pooled
+        fa = yf.amax.clone()
+        yf = yf.t.clone()
     E.STEM_POOL = False
     try:
         with eng.prec("trunk"):
             ys = eng.stem(x, flip, pool=True)
-            assert not getattr(ys, "_prpe_pooled", False)
-            B, H, W, C = ys.shape
-            yu = ops.maxpool(ys, torch.empty(B, H // 2, W // 2, C, device="cuda"), 3, 2, 1)
-            ua = ys._prpe_amax.clone()
+            assert not ys.pooled
+            B, H, W, C = ys.t.shape
+            yu = ops.maxpool(ys.t, torch.empty(B, H // 2, W // 2, C, device="cuda"), 3, 2, 1)
+            ua = ys.amax.clone()
     finally:
         E.STEM_POOL = True
     torch.cuda.synchronize()
@@ -52,9 +52,9 @@ def test_stem_maxpool_bit_identical_to_unfused(eng, N, H, W, flip):
 def test_stem_maxpool_deterministic_and_frame_independent(eng):
     x = synth.frames(48).cuda()
     with eng.prec("trunk"):
-        a = eng.stem(x, pool=True).clone()
-        b = eng.stem(x, pool=True).clone()
-        c = eng.stem(x[[0, 37]].contiguous(), pool=True).clone()
+        a = eng.stem(x, pool=True).t.clone()
+        b = eng.stem(x, pool=True).t.clone()
+        c = eng.stem(x[[0, 37]].contiguous(), pool=True).t.clone()
     torch.cuda.synchronize()
     assert torch.equal(a, b)
     assert torch.equal(a[37], c[1]) and torch.equal(a[0], c[0])

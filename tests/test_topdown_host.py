@@ -374,5 +374,5 @@ def test_crop_buffer_is_a_kind_of_its_own():
     assert a.shape == (2, 260, 196, 4) and b.shape == (5, 260, 196, 4)
     assert e.vit_pix4(2) is a and e.crop_pix4(5) is b and e.vit_pix4(2) is a
     pix = e.pix4_interior(b[:3])
-    assert pix.shape == (3, 256, 192, 3) and pix._prpe_pix4.data_ptr() == b.data_ptr()
-    assert pix.data_ptr() == b[0, 2, 2].data_ptr()
+    assert pix.t.shape == (3, 256, 192, 3) and pix.pix4.data_ptr() == b.data_ptr()
+    assert pix.t.data_ptr() == b[0, 2, 2].data_ptr()

@@ -32,19 +32,19 @@ def main():
 
     def conv(self, x, p, *args, **kw):
         y = conv0(self, x, p, *args, **kw)
-        rec.append((p.name, y[sel[0]].detach().float().cpu().clone()))
+        rec.append((p.name, y.t[sel[0]].detach().float().cpu().clone()))
         return y
 
     def bneck(self, q, x, **kw):
         y = bn0(self, q, x, **kw)
-        rec.append((q + ":x_amax", x._prpe_amax[sel[0]:sel[0] + 1].detach().cpu().clone()))
-        rec.append((q, y[sel[0]].detach().cpu().clone()))
-        rec.append((q + ":y_amax", y._prpe_amax[sel[0]:sel[0] + 1].detach().cpu().clone()))
+        rec.append((q + ":x_amax", x.amax[sel[0]:sel[0] + 1].detach().cpu().clone()))
+        rec.append((q, y.t[sel[0]].detach().cpu().clone()))
+        rec.append((q + ":y_amax", y.amax[sel[0]:sel[0] + 1].detach().cpu().clone()))
         return y
 
     def upconv(self, name, *args, **kw):
         y = up0(self, name, *args, **kw)
-        rec.append((name + ":up", y[sel[0]].detach().float().cpu().clone()))
+        rec.append((name + ":up", y.t[sel[0]].detach().float().cpu().clone()))
         return y
 
     E.Engine.conv, E.Engine.bottleneck, E.Engine.upconv = conv, bneck, upconv

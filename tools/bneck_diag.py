@@ -28,7 +28,7 @@ def main():
     for fuse in (True, False):
         engine.BNECK_FUSE = fuse
         m = CombinedModel(sd, device="cuda")
-        feats[fuse] = m.engine.trunk(x.cuda()).permute(0, 3, 1, 2).cpu().double()
+        feats[fuse] = m.engine.trunk(x.cuda()).t.permute(0, 3, 1, 2).cpu().double()
     print("fused vs unfused trunk: max|d|", (feats[True] - feats[False]).abs().max().item(),
           "bit-identical frac", (feats[True] == feats[False]).double().mean().item())
     engine.BNECK_FUSE = True
@@ -37,7 +37,7 @@ def main():
         e = m.engine
         feat = e.trunk(x.cuda())
         det = e.yolo("yolo_face", feat, [8.0, 16.0, 32.0]).cpu().double()
-        f = feat.permute(0, 3, 1, 2).cpu().double()
+        f = feat.t.permute(0, 3, 1, 2).cpu().double()
         print(f"policy={pol}: feat err {((f - f64).abs().max() / f64.abs().max()).item():.3e} "
               f"box max|d| {(det[:, :4] - d64[:, :4]).abs().max().item():.3f} "
               f"cls {(det[:, 4] - d64[:, 4]).abs().max().item():.2e}")

@@ -31,7 +31,7 @@ def main():
         feat = R.resnet50_trunk(sd, x)
     e = Engine(sd, "cuda")
     g = e.trunk(x.cuda())
-    err("trunk feat", g.permute(0, 3, 1, 2), feat)
+    err("trunk feat", g.t.permute(0, 3, 1, 2), feat)
     featd = feat.permute(0, 2, 3, 1).contiguous().cuda()
 
     # ---- ViT adapter + backbone
@@ -39,7 +39,7 @@ def main():
         pix = R.vitpose_adapter(sd, feat)
         heat = R.vitpose_backbone(sd, pix)
     gp = e.vit_adapter(featd)
-    err("vit adapter pixel_values", gp.permute(0, 3, 1, 2), pix)
+    err("vit adapter pixel_values", gp.t.permute(0, 3, 1, 2), pix)
     gh = e.vit_backbone(pix.permute(0, 2, 3, 1).contiguous().cuda())
     err("vit backbone heatmaps (oracle pix)", gh, heat)
     err("vit full branch heatmaps", e.vitpose(featd), heat)
@@ -64,9 +64,9 @@ def main():
         print("yolo adapter out per-channel std:", y.std(dim=(2, 3)).flatten().tolist())
         det = R.yolo_branch(sd, "yolo_face", feat, (8.0, 16.0, 32.0))
     gt = e.conv(featd, e.pk(a + ".0", a + ".0.weight", bn=a + ".1", bias_key=a + ".0.bias", act="silu"))
-    err("yolo adapter.0", gt.permute(0, 3, 1, 2), t)
+    err("yolo adapter.0", gt.t.permute(0, 3, 1, 2), t)
     gu = e.upconv(a + ".4", gt, a + ".4.weight", (160, 160), True, bn=a + ".5", bias_key=a + ".4.bias", act="silu")
-    err("yolo adapter upconv", gu.permute(0, 3, 1, 2), u)
+    err("yolo adapter upconv", gu.t.permute(0, 3, 1, 2), u)
     gd = e.yolo("yolo_face", featd, (8.0, 16.0, 32.0))
     err("yolo det cls", gd[:, 4], det[:, 4])
     err("yolo det box", gd[:, :4], det[:, :4])

@@ -14,6 +14,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "person-recognition-for-pose-estimation
 import torch  # noqa: E402
 
 from prpe import CombinedModel, arch, synth  # noqa: E402
+from prpe.engine import Act  # noqa: E402
 
 
 def main():
@@ -34,11 +35,11 @@ def main():
         with e.prec("trunk"):
             o = torch.relu(torch.randn(B, 160, 160, 64, device="cuda"))
             xs = torch.relu(torch.randn(B, 160, 160, 64, device="cuda"))
-        o._prpe_amax = o.abs().flatten(1).amax(1).contiguous()
-        xs._prpe_amax = xs.abs().flatten(1).amax(1).contiguous()
+        o = Act(o, o.abs().flatten(1).amax(1).contiguous())
+        xs = Act(xs, xs.abs().flatten(1).amax(1).contiguous())
         for _ in range(a.iters):
             with e.prec("trunk"):
-                e.conv(o, e.pk_dual("backbone.layer1.0"), x2=xs, x2_amax=xs._prpe_amax)
+                e.conv(o, e.pk_dual("backbone.layer1.0"), x2=xs)
     torch.cuda.synchronize()
     print("ok", a.what, B)
 
