@@ -582,6 +582,84 @@ int prpe_gallery_topk(const float* queries, int64_t q_row_stride, int32_t Q, int
                       const int64_t* labels, float threshold, int64_t* ident, void* workspace,
                       int64_t workspace_bytes, void* stream);
 
+/*
+ * Per-face identification: face boxes -> 112 x 112 crops in the stem's buffer -> the trunk ->
+ * AdaFace -> the gallery, and the join of identities to skeletons (csrc/roi.hip).
+ * The reference trains its face branch on 112 x 112 face images through the shared trunk
+ * (training/lightning/face_recognition/datamodule.py:41,80) but has no crop stage; the semantics
+ * are this project's. crop_meta, n_crops and status are the top-down stage's (above).
+ *
+ * roi_select: prpe_crop_select with the output size as arguments. Candidate rule, skip rules,
+ *   slot order, status bits and crop_meta layout are prpe_crop_select's; the window arithmetic is
+ *   its statements in its order (fp32, never fused) with the aspect a = (float)out_w / (float)out_h:
+ *   cx = (x1+x2)*0.5, cy = (y1+y2)*0.5; w = x2-x1, h = y2-y1; w > a*h ? h = w/a : w = h*a;
+ *   w *= pad, h *= pad; x0 = cx - 0.5*w, y0 = cy - 0.5*h. At out_h = 256, out_w = 192 the output
+ *   has prpe_crop_select's bits. -EINVAL as prpe_crop_select, and for out_h or out_w outside
+ *   1..4096.
+ * roi_resize: frames = a strided view [B, H, W, 3] (any strides); y = a view
+ *   [max_crops, out_h, out_w, 4], the interior of any zero-bordered NHWC4 buffer (the stem's
+ *   [n, 112+6, 112+8, 4] at rows / columns 3..114, the top-down crop buffer, ...): channel stride 1,
+ *   16-byte aligned, the other strides multiples of 4 floats (prpe_frame_ingest's conditions on its
+ *   y). The output size is the view's. Slot s < *n_crops: y[s, i, j, 0:3] = the bilinear sample at
+ *     (x0 + (j+0.5)*w/out_w - 0.5, y0 + (i+0.5)*h/out_h - 0.5),
+ *   taps outside the frame 0 (torch's grid_sample(bilinear, zeros, align_corners=False)), with
+ *   prpe_crop_resize's arithmetic: coordinates in fp64, clamped to [-2, size+1] before they become
+ *   indices (a NaN coordinate becomes -2: all taps outside), each weight rounded to fp32 once, two
+ *   fp32 lerps v00 + ax*(v01 - v00). y[s, i, j, 3] = 0, in the pixel's one 16-byte store. Slots at
+ *   or past *n_crops, and slots whose frame index is outside [0, B): zeros. Nothing outside the
+ *   view is addressed. Into the top-down crop buffer's interior the bits are prpe_crop_resize's.
+ *   y_amax (optional): device [max_crops], zeroed by the caller; y_amax[s] is raised to max|y[s]|
+ *   over the slot's interior (one atomicMax on the bit pattern per workgroup; a workgroup never
+ *   spans two slots). An empty slot, or a slot whose pixels are all 0, leaves it untouched.
+ * roi_resize_u8: the same reading uint8 frames [B, H, W, 3]: taps outside the frame contribute raw
+ *   0, and every pixel of a filled slot is raw * a[c] + b[c] (an fp32 multiply, then an add; a, b:
+ *   HOST arrays of 3 floats; swap_rb != 0: output channel c reads source channel 2 - c), as
+ *   prpe_crop_resize_u8. Empty slots are exact zeros. The bits are those of roi_resize on the
+ *   frames converted to float when a = 1, b = 0.
+ * -EINVAL, nothing launched: a null pointer (y_amax may be null), frames->c != 3, a frame side
+ *   outside 1..2^24, max_crops < 1 or != y->n, y->c != 4, a y that is not channel-contiguous,
+ *   16-byte aligned with strides that are multiples of 4, an output side above 4096.
+ *
+ * face_person_match: identities (of faces) to skeletons (of persons), one wavefront per frame, no
+ *   workspace, no atomics: two runs give the same bits.
+ *   Persons: crop_meta_p [max_p][8], n_p [1], keypoints [max_p][K][3] = (x, y, score) in frame
+ *   pixels (prpe_crop_keypoints). Faces: crop_meta_f [max_f][8], n_f [1], ident [max_f] int64,
+ *   score [max_f]. Both lists in the pixels of the same B frames. A frame's persons / faces are the
+ *   slots below n_p / n_f with its frame index, in ascending slot order.
+ *   Head point of a person: x and y summed over the keypoints k < head_kpts (5 for COCO: nose,
+ *   eyes, ears) with score >= kp_thr, in ascending k, in fp32, each sum divided by (float)count;
+ *   with count 0 the point (x0 + 0.5f*w, y0 + 0.25f*h) of the person's window.
+ *   Face centre: (x0 + 0.5f*w, y0 + 0.5f*h) of the face's window.
+ *   A (person, face) pair is eligible when the face centre lies inside the person's window
+ *   (cx >= x0, cx <= x0 + w, cy >= y0, cy <= y0 + h; fp32 sums) and its cost is finite.
+ *   Cost: dx*dx + dy*dy with dx, dy = head point - face centre (two fp32 products and a sum, never
+ *   fused).
+ *   Assignment: greedy one-to-one. Repeatedly the eligible pair of least cost among the unmatched
+ *   persons and faces is matched, ties to the lower person slot, then the lower face slot, until
+ *   no eligible pair is left.
+ *   Outputs per person slot: face_slot [max_p] int32 (the matched face's slot, else -1),
+ *   person_ident [max_p] int64 (ident of that face, else -1), person_score [max_p] (score of that
+ *   face, else -inf). Slots at or past n_p, and slots whose frame index is outside [0, B), get
+ *   (-1, -1, -inf). status [B] int32: 1 for a frame with more than 32 persons or more than 32
+ *   faces, which gets no matches (the other frames are unaffected), else 0.
+ * -EINVAL, nothing launched: a null pointer, max_p, max_f, B or K below 1, head_kpts outside
+ *   1..K, a NaN kp_thr.
+ */
+int prpe_roi_select(const float* dets, const int32_t* counts, int32_t B, int32_t max_det, float score_thr,
+                    int32_t max_per_frame, float min_size, float box_scale_x, float box_scale_y, int32_t H,
+                    int32_t W, float pad, int32_t out_h, int32_t out_w, int32_t max_crops, float* crop_meta,
+                    int32_t* n_crops, int32_t* status, void* stream);
+int prpe_roi_resize(const prpe_view* frames, const float* crop_meta, const int32_t* n_crops, int32_t max_crops,
+                    const prpe_view* y, float* y_amax /* optional */, void* stream);
+int prpe_roi_resize_u8(const prpe_view_u8* frames, const float* crop_meta, const int32_t* n_crops,
+                       int32_t max_crops, const float* a, const float* b, int32_t swap_rb, const prpe_view* y,
+                       float* y_amax /* optional */, void* stream);
+int prpe_face_person_match(const float* crop_meta_p, const int32_t* n_p, int32_t max_p, const float* keypoints,
+                           int32_t K, const float* crop_meta_f, const int32_t* n_f, int32_t max_f,
+                           const int64_t* ident, const float* score, float kp_thr, int32_t head_kpts, int32_t B,
+                           int32_t* face_slot, int64_t* person_ident, float* person_score, int32_t* status,
+                           void* stream);
+
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse
  * a library built from other sources than the ones beside it. */

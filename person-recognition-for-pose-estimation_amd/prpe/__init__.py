@@ -9,6 +9,7 @@ torch.distributed (RCCL) only.
 """
 from .arch import TASKS, state_dict_spec  # noqa: F401
 from .evalsteps import PoseEvalStep  # noqa: F401
+from .faces import FaceCrops, PersonRecognition  # noqa: F401
 from .gallery import FaceGallery, FaceIdentifier  # noqa: F401
 from .ingest import FrameIngest  # noqa: F401
 from .model import CombinedModel, PoseOutput  # noqa: F401
@@ -16,5 +17,6 @@ from .postproc import keypoints_from_heatmaps, non_max_suppression, non_max_supp
 from .topdown import TopDownPose  # noqa: F401
 
 __all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "TopDownPose", "FrameIngest", "FaceGallery", "FaceIdentifier",
+           "FaceCrops", "PersonRecognition",
            "non_max_suppression",
            "non_max_suppression_padded", "keypoints_from_heatmaps", "state_dict_spec", "TASKS"]

@@ -36,6 +36,8 @@ VIT_GRID = (16, 12)          # (256+4-16)//16+1, (192+4-16)//16+1  (patch conv p
 NUM_KEYPOINTS = 17
 HEATMAP = (64, 48)
 ADAFACE_CLASSES = 85742
+FACE_IMG = (112, 112)        # what the face branch is trained on (face_recognition/datamodule.py:41,80)
+HEAD_KEYPOINTS = 5           # COCO order: nose, eyes, ears come first
 
 TASKS = ("face_detection", "person_detection", "pose_estimation", "face_recognition")
 

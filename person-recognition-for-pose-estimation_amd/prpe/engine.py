@@ -453,6 +453,29 @@ class Engine:
             y.epoch = ("trunk", self._amax_epoch.get("trunk"))
             return y
 
+    # ---- the per-face crops (prpe.faces): FACE_IMG crops in a stem buffer of their own
+    def face_stem_buf(self, n):
+        """The stem's zero-bordered NHWC4 buffer for ``n`` face crops, [n, 112+6, 112+8, 4]
+        (prpe_roi_resize fills rows / columns 3..114). A kind of its own, as ``crop_pix4``: the
+        frames' ``stem_buf`` (batch B) and this one (batch max_crops) alternate without either
+        being reallocated."""
+        H, W = arch.FACE_IMG
+        return self._batch_buf("face_stem_buf", n, (H + 6, W + 8, 4))
+
+    def trunk_from_stem_buf(self, buf, fill, H0, W0):
+        """``trunk`` from a stem buffer [n, H0+6, W0+8, 4] that ``fill(interior, amax)`` fills
+        inside the trunk's scope: ``interior`` = buf[:, 3:3+H0, 3:3+W0, :], ``amax`` = [n] zeroed
+        max|x| slots of the trunk's pool (None below precision 3) that the fill raises, as
+        ``stem_u8``'s ingest does. Entering the scope re-zeroes the trunk pool: every head that
+        reads an earlier trunk output at ``feat_prec`` must have run before this call."""
+        with self.prec("trunk"):
+            n = buf.shape[0]
+            amax = self.amax_slot(n) if self.precision == 3 else None
+            fill(buf[:, 3:3 + H0, 3:3 + W0, :], amax)
+            y = self._trunk_layers(self._stem_conv(buf, amax, H0, W0, pool=True))
+            y.epoch = ("trunk", self._amax_epoch.get("trunk"))
+            return y
+
     def _trunk(self, x_nchw, flip_w=False):
         return self._trunk_layers(self.stem(x_nchw, flip_w, pool=True))
 

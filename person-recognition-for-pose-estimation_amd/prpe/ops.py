@@ -611,6 +611,126 @@ def crop_resize_u8(frames, crop_meta, n_crops, crops, a=(1.0, 1.0, 1.0), b=(0.0,
     return crops
 
 
+# ------------------------------------------------------------------ per-face crops and the match (csrc/roi.hip)
+ROI_MAX_OUT = 4096                   # largest output side of roi_select / roi_resize
+MATCH_MAX_PER_FRAME = 32             # persons / faces per frame face_person_match takes
+
+
+def roi_select(dets, counts, frame_hw, out_hw, *, crop_meta, n_crops, status, score_thr=0.25, max_per_frame=8,
+               min_size=4.0, box_scale=(1.0, 1.0), pad=1.25):
+    """``crop_select`` for an ``out_hw`` = (out_h, out_w) output: the window takes the aspect
+    out_w / out_h (prpe_roi_select, include/prpe.h). Everything else is ``crop_select``'s; at
+    (256, 192) so are the bits. No host read."""
+    what = "prpe_roi_select"
+    if not (isinstance(dets, torch.Tensor) and dets.dim() == 3 and dets.shape[2] == 6):
+        raise ValueError(f"{what}: dets must be [B, max_det, 6]")
+    B, max_det, _ = dets.shape
+    _check_dev(what, "dets", dets, torch.float32, (B, max_det, 6))
+    _check_dev(what, "counts", counts, torch.int32, (B,))
+    if not (isinstance(crop_meta, torch.Tensor) and crop_meta.dim() == 2):
+        raise ValueError(f"{what}: crop_meta must be [max_crops, {CROP_META_COLS}]")
+    max_crops = crop_meta.shape[0]
+    _check_dev(what, "crop_meta", crop_meta, torch.float32, (max_crops, CROP_META_COLS))
+    _check_dev(what, "n_crops", n_crops, torch.int32, (1,))
+    _check_dev(what, "status", status, torch.int32, (1,))
+    H, W = (int(v) for v in frame_hw)
+    oh, ow = (int(v) for v in out_hw)
+    sx, sy = (float(v) for v in box_scale)
+    if B < 1 or max_det < 1 or max_crops < 1 or max_per_frame < 1 or H < 1 or W < 1:
+        raise ValueError(f"{what}: empty batch, crop list or frame")
+    if not (1 <= oh <= ROI_MAX_OUT and 1 <= ow <= ROI_MAX_OUT):
+        raise ValueError(f"{what}: the output size {(oh, ow)} must be within 1..{ROI_MAX_OUT}")
+    check(lib().prpe_roi_select(dets.data_ptr(), counts.data_ptr(), B, max_det, float(score_thr), int(max_per_frame),
+                                float(min_size), sx, sy, H, W, float(pad), oh, ow, max_crops, crop_meta.data_ptr(),
+                                n_crops.data_ptr(), status.data_ptr(), _stream()), what)
+    return crop_meta, n_crops, status
+
+
+def _roi_args(what, crop_meta, n_crops, y, y_amax):
+    """The checks roi_resize and roi_resize_u8 share; returns max_crops."""
+    if not (isinstance(crop_meta, torch.Tensor) and crop_meta.dim() == 2):
+        raise ValueError(f"{what}: crop_meta must be [max_crops, {CROP_META_COLS}]")
+    max_crops = crop_meta.shape[0]
+    _check_dev(what, "crop_meta", crop_meta, torch.float32, (max_crops, CROP_META_COLS))
+    _check_dev(what, "n_crops", n_crops, torch.int32, (1,))
+    if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 4):
+        raise ValueError(f"{what}: y must be a float32 device tensor [max_crops, out_h, out_w, 4]")
+    if max_crops < 1 or y.shape[0] != max_crops or y.shape[3] != 4 or y.stride(3) != 1 or y.data_ptr() % 16 or \
+            any(s % 4 for s in y.stride()[:3]) or not (1 <= y.shape[1] <= ROI_MAX_OUT and 1 <= y.shape[2] <= ROI_MAX_OUT):
+        raise ValueError(f"{what}: y must be [{max_crops}, out_h, out_w, 4] (sides 1..{ROI_MAX_OUT}) with 4 contiguous, "
+                         f"16-byte aligned channels, got {list(y.shape)} strides {list(y.stride())}")
+    _check_slots(what, max_crops, y_amax)
+    return max_crops
+
+
+def roi_resize(frames, crop_meta, n_crops, y, y_amax=None):
+    """Resample the windows of ``crop_meta`` from ``frames`` ([B, 3, H, W] float32 device, any
+    strides) into ``y`` [max_crops, out_h, out_w, 4], the interior of a zero-bordered NHWC4 buffer
+    (Engine.face_stem_buf's, Engine.crop_pix4's; prpe_roi_resize, include/prpe.h). Slots at or
+    past n_crops are zeroed. ``y_amax`` ([max_crops] device, zeroed): raised to max|y[s]| per slot."""
+    what = "prpe_roi_resize"
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.float32 and
+            frames.dim() == 4 and frames.shape[1] == 3 and frames.numel() > 0):
+        raise ValueError(f"{what}: frames must be a float32 device tensor [B, 3, H, W]")
+    max_crops = _roi_args(what, crop_meta, n_crops, y, y_amax)
+    check(lib().prpe_roi_resize(C.byref(view(nhwc(frames))), crop_meta.data_ptr(), n_crops.data_ptr(), max_crops,
+                                C.byref(view(y)), _ptr(y_amax), _stream()), what)
+    return y
+
+
+def roi_resize_u8(frames, crop_meta, n_crops, y, a=(1.0, 1.0, 1.0), b=(0.0, 0.0, 0.0), swap_rb=False, y_amax=None):
+    """``roi_resize`` from uint8 source frames [B, Hs, Ws, 3] (any strides), every pixel of a
+    filled slot then raw * a[c] + b[c] (prpe_roi_resize_u8, include/prpe.h); the windows of
+    ``crop_meta`` are in the pixels of these frames."""
+    what = "prpe_roi_resize_u8"
+    fv = _u8_frames(what, frames)
+    max_crops = _roi_args(what, crop_meta, n_crops, y, y_amax)
+    check(lib().prpe_roi_resize_u8(C.byref(fv), crop_meta.data_ptr(), n_crops.data_ptr(), max_crops,
+                                   _f3(what, "a", a), _f3(what, "b", b), int(bool(swap_rb)), C.byref(view(y)),
+                                   _ptr(y_amax), _stream()), what)
+    return y
+
+
+def face_person_match(crop_meta_p, n_p, keypoints, crop_meta_f, n_f, ident, score, n_frames, *, face_slot,
+                      person_ident, person_score, status, kp_thr=0.3, head_kpts=5):
+    """Identities to skeletons (prpe_face_person_match, include/prpe.h): the person list
+    (crop_meta_p [P, 8], n_p [1], keypoints [P, K, 3] in frame pixels) and the face list
+    (crop_meta_f [F, 8], n_f [1], ident [F] int64, score [F]) of the same ``n_frames`` frames ->
+    per person slot face_slot [P] int32, person_ident [P] int64, person_score [P]; status
+    [n_frames] int32 (1: more than 32 persons or faces in the frame, no matches there). A face goes
+    to the person whose head point (mean of the first ``head_kpts`` keypoints with score >=
+    ``kp_thr``) is nearest among the persons whose window holds the face centre, greedily and
+    one-to-one. No host read."""
+    what = "prpe_face_person_match"
+    for name, t in (("crop_meta_p", crop_meta_p), ("crop_meta_f", crop_meta_f)):
+        if not (isinstance(t, torch.Tensor) and t.dim() == 2):
+            raise ValueError(f"{what}: {name} must be [slots, {CROP_META_COLS}]")
+    if not (isinstance(keypoints, torch.Tensor) and keypoints.dim() == 3 and keypoints.shape[2] == 3):
+        raise ValueError(f"{what}: keypoints must be [P, K, 3]")
+    P, F = crop_meta_p.shape[0], crop_meta_f.shape[0]
+    K, B = keypoints.shape[1], int(n_frames)
+    _check_dev(what, "crop_meta_p", crop_meta_p, torch.float32, (P, CROP_META_COLS))
+    _check_dev(what, "n_p", n_p, torch.int32, (1,))
+    _check_dev(what, "keypoints", keypoints, torch.float32, (P, K, 3))
+    _check_dev(what, "crop_meta_f", crop_meta_f, torch.float32, (F, CROP_META_COLS))
+    _check_dev(what, "n_f", n_f, torch.int32, (1,))
+    _check_dev(what, "ident", ident, torch.int64, (F,))
+    _check_dev(what, "score", score, torch.float32, (F,))
+    _check_dev(what, "face_slot", face_slot, torch.int32, (P,))
+    _check_dev(what, "person_ident", person_ident, torch.int64, (P,))
+    _check_dev(what, "person_score", person_score, torch.float32, (P,))
+    _check_dev(what, "status", status, torch.int32, (max(B, 0),))
+    head_kpts, kp_thr = int(head_kpts), float(kp_thr)
+    if P < 1 or F < 1 or B < 1 or K < 1 or not 1 <= head_kpts <= K or kp_thr != kp_thr:
+        raise ValueError(f"{what}: P = {P}, F = {F}, frames = {B}, head_kpts = {head_kpts} of K = {K}, "
+                         f"kp_thr = {kp_thr}")
+    check(lib().prpe_face_person_match(crop_meta_p.data_ptr(), n_p.data_ptr(), P, keypoints.data_ptr(), K,
+                                       crop_meta_f.data_ptr(), n_f.data_ptr(), F, ident.data_ptr(), score.data_ptr(),
+                                       kp_thr, head_kpts, B, face_slot.data_ptr(), person_ident.data_ptr(),
+                                       person_score.data_ptr(), status.data_ptr(), _stream()), what)
+    return face_slot, person_ident, person_score, status
+
+
 # ------------------------------------------------------------------ face identification (csrc/gallery.hip)
 GALLERY_MAX_K = 8
 GALLERY_MAX_DIM = 512
