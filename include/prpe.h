@@ -660,6 +660,75 @@ int prpe_face_person_match(const float* crop_meta_p, const int32_t* n_p, int32_t
                            int32_t* face_slot, int64_t* person_ident, float* person_score, int32_t* status,
                            void* stream);
 
+/*
+ * Tracking: persons associated across frames, so that a skeleton keeps its track id and the name
+ * once read from its face (csrc/track.hip). The reference has no tracker; the
+ * semantics are this project's, after the greedy IoU / OKS trackers of top-down pose demos, with
+ * no exp so that a host restatement matches bit for bit. One wavefront per stream walks the
+ * stream's frames in order with the track table on chip: one launch, no workspace, no atomics, no
+ * host read; two runs give the same bits. Streams are independent of each other and of the slot
+ * order of other streams' persons.
+ *
+ * track_update.
+ *   Persons: crop_meta_p [max_p][8], n_p [1], keypoints [max_p][K][3] = (x, y, score) in frame
+ *   pixels, person_ident [max_p] int64 and person_score [max_p] as face_person_match leaves them.
+ *   A frame's persons are the slots below n_p with its frame index, in ascending slot order. A
+ *   person carries an identity when person_ident >= 0 and person_score is finite; its identity
+ *   pair is then (person_ident, person_score), else (-1, -inf).
+ *   Frames: frame_stream [B] int32 (device) is the stream of frame b; a value outside [0, S): the
+ *   frame is not tracked. A stream's frames are taken in ascending b (its time order).
+ *   State (the caller's, persistent between calls, T = 32 track slots per stream):
+ *   trk_meta [S][32][8] = (id, age, hits as int32 bits; window x0, y0, w, h; the last detection
+ *   score), trk_kpts [S][32][K][3], trk_ident [S][32] int64, trk_iscore [S][32], next_id [S]
+ *   int32. A free slot has id -1; a track is live when id >= 0. A fresh state is id -1, ident -1,
+ *   iscore -inf in every slot and next_id 0 (the other columns may hold anything). The call reads
+ *   the state, walks the frames and writes every row back once at the end; a freed slot keeps the
+ *   other columns and keypoints it had.
+ *   Cost of a (track, person) pair, all fp32, each product, sum and quotient rounded once and
+ *   nothing fused:
+ *     mode 0 (windows, a = track, b = person):
+ *       ix = min(x0a+wa, x0b+wb) - max(x0a, x0b), then ix < 0 ? 0 : ix; iy likewise from y0, h;
+ *       inter = ix*iy; uni = wa*ha + wb*hb - inter (left to right); c = 1 - inter/uni.
+ *       min(u, v) = v < u ? v : u and max(u, v) = v > u ? v : u (a NaN second operand loses).
+ *     mode 1 (skeletons): over the keypoints k in ascending k whose score is >= kp_thr in both
+ *       the track and the person: dx, dy = person - track; d_k = (dx*dx + dy*dy) / (area * k2[k])
+ *       with area = w*h of the track's window; sum = 0, then sum = sum + d_k;
+ *       c = sum / (float)count. count < min_common: the pair is not eligible. k2[k] =
+ *       (2 sigma_k)^2 (HOST, K floats). This is the exponent of OKS averaged, not OKS: there is no
+ *       exp and no factor 2, and the gate is on this quantity.
+ *   A pair is eligible when c is finite and c <= gate.
+ *   One frame b of stream s, in this order:
+ *   1. More than 32 persons: status[b] = 1 and the frame is skipped whole; the stream's tracks
+ *      are neither matched nor aged, its persons get the no-track outputs.
+ *   2. Association, greedy and one-to-one over the live tracks and the frame's persons:
+ *      repeatedly the eligible pair of least c among the unmatched is matched (-0 equals +0), ties
+ *      to the lower track slot, then the lower person slot, until no eligible pair is left.
+ *   3. A matched track takes the person's window, keypoints and detection score; age = 0,
+ *      hits += 1. A person that carries (ident, s): ident == trk_ident: trk_iscore =
+ *      s > trk_iscore ? s : trk_iscore; else if s > trk_iscore: (trk_ident, trk_iscore) =
+ *      (ident, s); otherwise, and for a person without an identity, nothing changes.
+ *   4. Every unmatched live track: age += 1; age > max_age: freed (id -1, ident -1, iscore -inf).
+ *   5. The unmatched persons with detection score >= new_thr, in ascending slot order, each
+ *      open a track in the lowest free slot (slots freed in step 4 included): id = next_id[s]++,
+ *      hits 1, age 0, the person's window, keypoints, score and identity pair. No free slot:
+ *      status[b] |= 2 and the person stays untracked.
+ *   status [B] int32: 0, 1 or 2 as above; 0 for a frame that is not tracked.
+ *   Outputs per person slot: track_id [max_p] int32, track_hits [max_p] int32, track_ident
+ *   [max_p] int64, track_iscore [max_p]: the track's values after the frame's update. Slots at or
+ *   past n_p, slots whose frame index is outside [0, B), persons of frames that are not tracked
+ *   or skipped, and unmatched persons that opened no track get (-1, 0, -1, -inf).
+ * -EINVAL, nothing launched and nothing written: a null pointer, B, S, K or max_p below 1, K above
+ *   64, max_p * K * 3 at or above 2^31, mode outside {0, 1}, a NaN gate, kp_thr or new_thr,
+ *   min_common outside 1..K, max_age below 0, a k2[k] that is not finite and positive.
+ */
+int prpe_track_update(const float* crop_meta_p, const int32_t* n_p, int32_t max_p, const float* keypoints,
+                      int32_t K, const int64_t* person_ident, const float* person_score,
+                      const int32_t* frame_stream, int32_t B, int32_t S, int32_t mode, float gate, float kp_thr,
+                      int32_t min_common, const float* k2 /* HOST: K floats */, float new_thr, int32_t max_age,
+                      float* trk_meta, float* trk_kpts, int64_t* trk_ident, float* trk_iscore, int32_t* next_id,
+                      int32_t* track_id, int32_t* track_hits, int64_t* track_ident, float* track_iscore,
+                      int32_t* status, void* stream);
+
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse
  * a library built from other sources than the ones beside it. */

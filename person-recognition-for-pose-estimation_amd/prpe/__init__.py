@@ -15,8 +15,9 @@ from .ingest import FrameIngest  # noqa: F401
 from .model import CombinedModel, PoseOutput  # noqa: F401
 from .postproc import keypoints_from_heatmaps, non_max_suppression, non_max_suppression_padded  # noqa: F401
 from .topdown import TopDownPose  # noqa: F401
+from .tracks import PersonTracker  # noqa: F401
 
 __all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "TopDownPose", "FrameIngest", "FaceGallery", "FaceIdentifier",
-           "FaceCrops", "PersonRecognition",
+           "FaceCrops", "PersonRecognition", "PersonTracker",
            "non_max_suppression",
            "non_max_suppression_padded", "keypoints_from_heatmaps", "state_dict_spec", "TASKS"]

@@ -111,6 +111,8 @@ SIGNATURES = {
     "prpe_roi_resize": (C.c_int, [_VP, _P, _P, _I, _VP, _P, _P]),
     "prpe_roi_resize_u8": (C.c_int, [_VP, _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _VP, _P, _P]),
     "prpe_face_person_match": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P]),
+    "prpe_track_update": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _F, _I, C.POINTER(C.c_float), _F, _I,
+                                    _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "prpe_abi_version": (C.c_int, []),
     "prpe_build_info": (C.c_char_p, []),
     "prpe_source_hash": (C.c_char_p, []),

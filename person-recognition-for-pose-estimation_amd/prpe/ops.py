@@ -731,6 +731,73 @@ def face_person_match(crop_meta_p, n_p, keypoints, crop_meta_f, n_f, ident, scor
     return face_slot, person_ident, person_score, status
 
 
+# ------------------------------------------------------------------ tracking across frames (csrc/track.hip)
+TRACK_SLOTS = 32                     # track slots per stream, and persons per frame track_update takes
+TRACK_MAX_K = 64                     # keypoints per person
+TRACK_MODES = {"iou": 0, "pose": 1}
+
+
+def track_update(crop_meta_p, n_p, keypoints, person_ident, person_score, frame_stream, *, trk_meta, trk_kpts,
+                 trk_ident, trk_iscore, next_id, track_id, track_hits, track_ident, track_iscore, status, k2,
+                 mode="iou", gate=0.7, kp_thr=0.3, min_common=3, new_thr=0.25, max_age=30):
+    """Persons to tracks (prpe_track_update, include/prpe.h): the person list (crop_meta_p [P, 8],
+    n_p [1], keypoints [P, K, 3] in frame pixels, person_ident [P] int64, person_score [P]) of B
+    frames whose streams are ``frame_stream`` [B] int32 (outside [0, S): not tracked), against the
+    caller's state of S streams x 32 slots (trk_meta [S, 32, 8], trk_kpts [S, 32, K, 3], trk_ident
+    [S, 32] int64, trk_iscore [S, 32], next_id [S] int32), updated in place -> per person slot
+    track_id, track_hits [P] int32, track_ident [P] int64, track_iscore [P]; status [B] int32
+    (1: more than 32 persons, the frame is skipped; 2: no free slot for a new track). ``mode``:
+    "iou" (cost 1 - IoU of the windows) or "pose" (mean squared keypoint distance over area *
+    k2[k]); ``k2``: K host floats, (2 sigma_k)^2. One wavefront per stream walks its frames in
+    ascending order; no host read."""
+    what = "prpe_track_update"
+    if not (isinstance(crop_meta_p, torch.Tensor) and crop_meta_p.dim() == 2):
+        raise ValueError(f"{what}: crop_meta_p must be [slots, {CROP_META_COLS}]")
+    if not (isinstance(keypoints, torch.Tensor) and keypoints.dim() == 3 and keypoints.shape[2] == 3):
+        raise ValueError(f"{what}: keypoints must be [P, K, 3]")
+    if not (isinstance(frame_stream, torch.Tensor) and frame_stream.dim() == 1):
+        raise ValueError(f"{what}: frame_stream must be [B]")
+    if not (isinstance(trk_meta, torch.Tensor) and trk_meta.dim() == 3):
+        raise ValueError(f"{what}: trk_meta must be [S, {TRACK_SLOTS}, 8]")
+    if mode not in TRACK_MODES:
+        raise ValueError(f"{what}: mode must be one of {sorted(TRACK_MODES)}, got {mode!r}")
+    P, K, B, S = crop_meta_p.shape[0], keypoints.shape[1], frame_stream.shape[0], trk_meta.shape[0]
+    T = TRACK_SLOTS
+    _check_dev(what, "crop_meta_p", crop_meta_p, torch.float32, (P, CROP_META_COLS))
+    _check_dev(what, "n_p", n_p, torch.int32, (1,))
+    _check_dev(what, "keypoints", keypoints, torch.float32, (P, K, 3))
+    _check_dev(what, "person_ident", person_ident, torch.int64, (P,))
+    _check_dev(what, "person_score", person_score, torch.float32, (P,))
+    _check_dev(what, "frame_stream", frame_stream, torch.int32, (B,))
+    _check_dev(what, "trk_meta", trk_meta, torch.float32, (S, T, 8))
+    _check_dev(what, "trk_kpts", trk_kpts, torch.float32, (S, T, K, 3))
+    _check_dev(what, "trk_ident", trk_ident, torch.int64, (S, T))
+    _check_dev(what, "trk_iscore", trk_iscore, torch.float32, (S, T))
+    _check_dev(what, "next_id", next_id, torch.int32, (S,))
+    _check_dev(what, "track_id", track_id, torch.int32, (P,))
+    _check_dev(what, "track_hits", track_hits, torch.int32, (P,))
+    _check_dev(what, "track_ident", track_ident, torch.int64, (P,))
+    _check_dev(what, "track_iscore", track_iscore, torch.float32, (P,))
+    _check_dev(what, "status", status, torch.int32, (B,))
+    k2 = [float(v) for v in k2]
+    gate, kp_thr, new_thr, min_common, max_age = float(gate), float(kp_thr), float(new_thr), int(min_common), int(max_age)
+    if P < 1 or B < 1 or S < 1 or not 1 <= K <= TRACK_MAX_K or len(k2) != K:
+        raise ValueError(f"{what}: P = {P}, frames = {B}, streams = {S}, K = {K} (1..{TRACK_MAX_K}) with {len(k2)} k2")
+    if gate != gate or kp_thr != kp_thr or new_thr != new_thr or not 1 <= min_common <= K or max_age < 0:
+        raise ValueError(f"{what}: gate = {gate}, kp_thr = {kp_thr}, new_thr = {new_thr}, min_common = {min_common} "
+                         f"of K = {K}, max_age = {max_age}")
+    if not all(0.0 < v < float("inf") for v in k2):
+        raise ValueError(f"{what}: every k2 must be finite and positive")
+    check(lib().prpe_track_update(crop_meta_p.data_ptr(), n_p.data_ptr(), P, keypoints.data_ptr(), K,
+                                  person_ident.data_ptr(), person_score.data_ptr(), frame_stream.data_ptr(), B, S,
+                                  TRACK_MODES[mode], gate, kp_thr, min_common, (C.c_float * K)(*k2), new_thr, max_age,
+                                  trk_meta.data_ptr(), trk_kpts.data_ptr(), trk_ident.data_ptr(),
+                                  trk_iscore.data_ptr(), next_id.data_ptr(), track_id.data_ptr(),
+                                  track_hits.data_ptr(), track_ident.data_ptr(), track_iscore.data_ptr(),
+                                  status.data_ptr(), _stream()), what)
+    return track_id, track_hits, track_ident, track_iscore, status
+
+
 # ------------------------------------------------------------------ face identification (csrc/gallery.hip)
 GALLERY_MAX_K = 8
 GALLERY_MAX_DIM = 512
