@@ -729,6 +729,80 @@ int prpe_track_update(const float* crop_meta_p, const int32_t* n_p, int32_t max_
                       int32_t* track_id, int32_t* track_hits, int64_t* track_ident, float* track_iscore,
                       int32_t* status, void* stream);
 
+/*
+ * COCO keypoint evaluation of an epoch's pose records (csrc/cocoeval.hip): what
+ * pycocotools' COCOeval(gt, dt, 'keypoints') computes in evaluate(), accumulate() and summarize(),
+ * in fp64 and in its operation order, on the records prpe_pose_coco_records left on the device.
+ * The library allocates nothing; no atomics: two runs give the same bits. Additive to ABI 12.
+ *
+ * Fixed sizes: 20 detections kept per image (maxDets), at most 64 ground-truth persons per image,
+ * 10 OKS thresholds, 101 recall thresholds, 3 area ranges (all, medium, large), K <= 64.
+ *
+ * Ground truth (device, CSR over I images in ascending image-id order): gt_start int32 [I+1],
+ *   gt_kpts double [G,K,3] (x, y, v), gt_bbox double [G,4] (x, y, w, h), gt_area double [G],
+ *   gt_iscrowd uint8 [G], gt_ignore uint8 [G] (iscrowd or num_keypoints == 0). max_gt: the HOST's
+ *   maximum of gt_start[i+1] - gt_start[i]; an image whose count is outside 0..64, or whose rows
+ *   leave [0, G), is taken as having no ground truth (nothing outside the arrays is addressed).
+ * Detections: rec_kpts [n,K,3], rec_meta [n,8] as pose_coco_records leaves them (column 0: image
+ *   slot as int32 bits, column 2: score); n = min(*counter, n_max) (counter null: n_max), n_max the
+ *   HOST's bound, at most the arrays' capacity. slot_to_img int32 [slots] (device): the image's row
+ *   in the ground-truth table; a record whose slot or row is out of range is dropped. The records
+ *   of one image must be one contiguous run.
+ * HOST constants: sigmas double [K], iou_thrs double [10], area_rngs double [3][2] (lo, hi),
+ *   rec_thrs double [101], ascending.
+ *
+ * coco_kp_match, per image i (one wavefront):
+ *   a. The image's records in descending score, stable in record order, NaN last; the first 20.
+ *      A detection's area: (max x - min x) * (max y - min y) over its K keypoints.
+ *   b. OKS of detection d and ground truth j, vars = (2 sigma)^2, k1 = #(v > 0):
+ *      k1 > 0: dx = xd - xg, dy = yd - yg; else with x0 = bx - bw, x1 = bx + 2 bw (y likewise)
+ *      dx = max(0, x0 - xd) + max(0, xd - x1); e = (dx^2 + dy^2) / vars / (area_j + 2^-52) / 2;
+ *      OKS = sum of exp(-e) over the keypoints with v > 0 (all K when k1 = 0), in ascending k,
+ *      over their count.
+ *   c. For each area range and threshold t: ground truth j is ignored when gt_ignore or its area
+ *      is outside [lo, hi]; the ground truth is walked with the ignored ones last, otherwise in
+ *      table order. A detection starts at iou = min(t, 1 - 1e-10), m = none; it skips a matched
+ *      ground truth that is no crowd, stops at an ignored one once m is not ignored, skips
+ *      oks < iou, else takes (iou, m) = (oks, j). Matched: it takes m's ignore flag and marks m.
+ *      Unmatched with its own area outside [lo, hi]: ignored.
+ *   d. Slot [i, rank], rank < 20: dt_score float, dt_rec int32 (the record's index, -1 when the
+ *      slot is empty), dt_bits uint64: bit a*10+t matched, bit 30+a*10+t ignored, bit 63 the slot
+ *      is empty. npig int32 [I,3]: ground truth not ignored per area range. oks_out (optional)
+ *      double [I,20,64]: [rank, j], -1 where there is no pair.
+ * coco_kp_accumulate: the I*20 slots sorted once by descending score (equal scores in slot order,
+ *   empty slots and NaN last); per (a, t) with npig = sum_i npig[i, a] > 0: tp / fp = running
+ *   counts of the matched / unmatched slots that are not ignored, rc = tp / npig,
+ *   pr = tp / (fp + tp + 2^-52), pr made non-increasing from the back, precision[t, r, a] = pr at
+ *   the first slot with rc >= rec_thrs[r] (0 if none), recall[t, a] = the last rc. npig = 0: -1.
+ *   precision double [10,101,3], recall double [10,3], stats double [10] = AP, AP50, AP75, APm,
+ *   APl, AR, AR50, AR75, ARm, ARl: means of the precision (recall) entries > -1 over all
+ *   thresholds (threshold 0 / 5 only for the 50 / 75 ones) of area range 0 (1 for m, 2 for l), summed
+ *   in index order; -1 without entries.
+ * -EINVAL, nothing launched and nothing written: a null pointer (oks_out and counter may be null;
+ *   the record arrays when n_max = 0 and the ground-truth arrays when G = 0 too), I < 1 or
+ *   I * 20 >= 2^31, K outside 1..64, G < 0, max_gt outside 0..64, n_max outside 0..2^31-1, a
+ *   workspace below *_workspace_bytes, a sigma that is not finite and positive, a NaN threshold or
+ *   range bound, rec_thrs that do not ascend strictly.
+ */
+#define PRPE_COCO_MAX_DETS 20
+#define PRPE_COCO_MAX_GT 64
+#define PRPE_COCO_IOU_THRS 10
+#define PRPE_COCO_REC_THRS 101
+#define PRPE_COCO_AREAS 3
+int64_t prpe_coco_kp_match_workspace_bytes(int32_t I);
+int prpe_coco_kp_match(const float* rec_kpts, const float* rec_meta, const uint64_t* counter /* optional */,
+                       int64_t n_max, const int32_t* slot_to_img, int32_t slots, const int32_t* gt_start,
+                       const double* gt_kpts, const double* gt_bbox, const double* gt_area,
+                       const uint8_t* gt_iscrowd, const uint8_t* gt_ignore, int32_t I, int32_t G, int32_t max_gt,
+                       int32_t K, const double* sigmas /* HOST */, const double* iou_thrs /* HOST */,
+                       const double* area_rngs /* HOST */, float* dt_score, uint64_t* dt_bits, int32_t* dt_rec,
+                       int32_t* npig, double* oks_out /* optional */, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+int64_t prpe_coco_kp_accumulate_workspace_bytes(int32_t I);
+int prpe_coco_kp_accumulate(const float* dt_score, const uint64_t* dt_bits, const int32_t* npig, int32_t I,
+                            const double* rec_thrs /* HOST */, double* precision, double* recall, double* stats,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse
  * a library built from other sources than the ones beside it. */

@@ -8,7 +8,7 @@ Device work: hand-written HIP kernels in ../csrc behind the C ABI of include/prp
 torch.distributed (RCCL) only.
 """
 from .arch import TASKS, state_dict_spec  # noqa: F401
-from .evalsteps import PoseEvalStep  # noqa: F401
+from .evalsteps import CocoKeypointGT, PoseEvalStep, coco_keypoint_eval  # noqa: F401
 from .faces import FaceCrops, PersonRecognition  # noqa: F401
 from .gallery import FaceGallery, FaceIdentifier  # noqa: F401
 from .ingest import FrameIngest  # noqa: F401
@@ -17,7 +17,8 @@ from .postproc import keypoints_from_heatmaps, non_max_suppression, non_max_supp
 from .topdown import TopDownPose  # noqa: F401
 from .tracks import PersonTracker  # noqa: F401
 
-__all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "TopDownPose", "FrameIngest", "FaceGallery", "FaceIdentifier",
+__all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "CocoKeypointGT", "coco_keypoint_eval",
+           "TopDownPose", "FrameIngest", "FaceGallery", "FaceIdentifier",
            "FaceCrops", "PersonRecognition", "PersonTracker",
            "non_max_suppression",
            "non_max_suppression_padded", "keypoints_from_heatmaps", "state_dict_spec", "TASKS"]

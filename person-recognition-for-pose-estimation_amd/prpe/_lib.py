@@ -113,6 +113,12 @@ SIGNATURES = {
     "prpe_face_person_match": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P]),
     "prpe_track_update": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _F, _I, C.POINTER(C.c_float), _F, _I,
                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "prpe_coco_kp_match_workspace_bytes": (C.c_int64, [_I]),
+    "prpe_coco_kp_match": (C.c_int, [_P, _P, _P, _L, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     _P, _P, _P, _P, _P, _P, _L, _P]),
+    "prpe_coco_kp_accumulate_workspace_bytes": (C.c_int64, [_I]),
+    "prpe_coco_kp_accumulate": (C.c_int, [_P, _P, _P, _I, C.POINTER(C.c_double), _P, _P, _P, _P, _L, _P]),
     "prpe_abi_version": (C.c_int, []),
     "prpe_build_info": (C.c_char_p, []),
     "prpe_source_hash": (C.c_char_p, []),

@@ -170,10 +170,135 @@ def format_coco_records(rec_kpts, rec_meta, slot_image_ids) -> list[dict]:
     return preds
 
 
+# COCOeval's Params for iouType 'keypoints' (fp64, as pycocotools builds them)
+COCO_KP_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
+COCO_IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+COCO_REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+COCO_KP_AREA_RNGS = [[0 ** 2, 1e5 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]     # all, medium, large
+COCO_KP_STAT_KEYS = ("val/AP", "val/AP50", "val/AP75", "val/APm", "val/APl",
+                     "val/AR", "val/AR50", "val/AR75", "val/ARm", "val/ARl")       # module.py:612-622
+
+
+class CocoKeypointGT:
+    """The person keypoint annotations of a COCO file as the table ``prpe_coco_kp_match`` reads:
+    images in ascending image-id order (COCOeval's ``params.imgIds``), each image's annotations in
+    file order, CSR. Built on the host from plain JSON (no pycocotools); ``to(device)`` uploads
+    it once per dataset."""
+
+    MAX_GT = ops.COCO_MAX_GT
+
+    def __init__(self, image_ids, gt_start, kpts, bbox, area, iscrowd, ignore):
+        self.image_ids = [int(i) for i in image_ids]
+        self.row_of = {i: r for r, i in enumerate(self.image_ids)}
+        self.gt_start = np.ascontiguousarray(gt_start, dtype=np.int32)
+        self.kpts = np.ascontiguousarray(kpts, dtype=np.float64)
+        self.bbox = np.ascontiguousarray(bbox, dtype=np.float64).reshape(-1, 4)
+        self.area = np.ascontiguousarray(area, dtype=np.float64)
+        self.iscrowd = np.ascontiguousarray(iscrowd, dtype=np.uint8)
+        self.ignore = np.ascontiguousarray(ignore, dtype=np.uint8)
+        self.K = int(self.kpts.shape[1])
+        counts = np.diff(self.gt_start)
+        self.max_gt = int(counts.max()) if len(counts) else 0
+        if len(self.image_ids) < 1:
+            raise ValueError("CocoKeypointGT: no images")
+        if self.max_gt > self.MAX_GT:
+            worst = self.image_ids[int(counts.argmax())]
+            raise ValueError(f"CocoKeypointGT: image {worst} has {self.max_gt} annotations, the device table "
+                             f"takes at most {self.MAX_GT} per image")
+        self.device = None
+        self._dev = None
+
+    @classmethod
+    def from_annotations(cls, annotations, image_ids=None, category_id: int = 1, num_keypoints: int | None = None,
+                         device=None):
+        """``annotations``: a path to a COCO JSON file, its dict ({"images": ..., "annotations": ...})
+        or a list of annotation dicts. ``image_ids`` adds images that have no annotation (a dict's
+        "images" are added by themselves). Annotations of other categories are left out."""
+        if isinstance(annotations, (str, bytes)) or hasattr(annotations, "__fspath__"):
+            import json
+            with open(annotations) as f:
+                annotations = json.load(f)
+        ids = set() if image_ids is None else {int(i) for i in image_ids}
+        if isinstance(annotations, dict):
+            ids |= {int(im["id"]) for im in annotations.get("images", [])}
+            annotations = annotations.get("annotations", [])
+        anns = [a for a in annotations if int(a.get("category_id", category_id)) == category_id]
+        ids |= {int(a["image_id"]) for a in anns}
+        ids = sorted(ids)
+        per = {i: [] for i in ids}
+        for a in anns:
+            per[int(a["image_id"])].append(a)
+        K = num_keypoints
+        if K is None:
+            K = len(anns[0]["keypoints"]) // 3 if anns else len(COCO_KP_SIGMAS)
+        start, kp, bb, ar, cr, ig = [0], [], [], [], [], []
+        for i in ids:
+            for a in per[i]:
+                k = np.asarray(a["keypoints"], dtype=np.float64)
+                if k.shape != (K * 3,):
+                    raise ValueError(f"CocoKeypointGT: annotation {a.get('id')} has {k.size} keypoint values, not {K * 3}")
+                k = k.reshape(K, 3)
+                crowd = bool(a.get("iscrowd", 0))
+                nk = a["num_keypoints"] if "num_keypoints" in a else int((k[:, 2] > 0).sum())
+                kp.append(k)
+                bb.append([float(v) for v in a["bbox"]])
+                ar.append(float(a["area"]))
+                cr.append(crowd)
+                ig.append(crowd or nk == 0)           # COCOeval._prepare for 'keypoints'
+            start.append(len(kp))
+        gt = cls(ids, start, np.stack(kp) if kp else np.zeros((0, K, 3)), np.asarray(bb, dtype=np.float64), ar, cr, ig)
+        return gt if device is None else gt.to(device)
+
+    def __len__(self):
+        return len(self.image_ids)
+
+    def to(self, device):
+        device = torch.device(device)
+        if self._dev is None or self.device != device:
+            self._dev = {k: torch.from_numpy(getattr(self, k)).to(device)
+                         for k in ("gt_start", "kpts", "bbox", "area", "iscrowd", "ignore")}
+            self.device = device
+        return self
+
+    def tensors(self) -> dict:
+        if self._dev is None:
+            raise ValueError("CocoKeypointGT: the table is on the host; call .to(device) first")
+        return self._dev
+
+    def slot_to_img(self, slot_image_ids) -> np.ndarray:
+        """Row in the table of every image slot of an epoch (int32). An image id that the
+        annotations do not know is refused, as ``COCO.loadRes`` asserts."""
+        rows = np.empty(len(slot_image_ids), dtype=np.int32)
+        for s, i in enumerate(slot_image_ids):
+            r = self.row_of.get(int(i))
+            if r is None:
+                raise ValueError(f"CocoKeypointGT: image id {int(i)} of the results is not in the annotations")
+            rows[s] = r
+        return rows
+
+
+def coco_keypoint_eval(rec_kpts, rec_meta, counter, n_max, slot_image_ids, gt: CocoKeypointGT,
+                       sigmas=None, want_oks=True) -> dict:
+    """``prpe_coco_kp_match`` + ``prpe_coco_kp_accumulate`` on device record arrays. Returns the
+    device tensors of both (dt_score, dt_bits, dt_rec, npig, oks, precision, recall, stats); reads
+    nothing back."""
+    dev = rec_kpts.device
+    t = gt.to(dev).tensors()
+    sigmas = COCO_KP_SIGMAS if sigmas is None else sigmas
+    rows = gt.slot_to_img(slot_image_ids)
+    s2i = torch.from_numpy(rows).to(dev) if len(rows) else torch.zeros(1, dtype=torch.int32, device=dev)
+    ev = ops.coco_kp_match(rec_kpts, rec_meta, counter, n_max, s2i, t["gt_start"], t["kpts"], t["bbox"], t["area"],
+                           t["iscrowd"], t["ignore"], gt.max_gt, sigmas, COCO_IOU_THRS, COCO_KP_AREA_RNGS,
+                           want_oks=want_oks)
+    ev.update(ops.coco_kp_accumulate(ev["dt_score"], ev["dt_bits"], ev["npig"], COCO_REC_THRS))
+    return ev
+
+
 class PoseEvalStep:
     """PoseEstimationModule.validation_step with everything after the model on the device.
 
-    ``step = PoseEvalStep(model); step.reset(); loss = step(batch); ...; step.predictions()``.
+    ``step = PoseEvalStep(model); step.reset(); loss = step(batch); ...; step.compute(gt)`` gives
+    on_validation_epoch_end's COCO metrics on the device; ``step.predictions()`` the records.
     ``batch`` is the reference's dict (images, keypoints [B,N,K,3], boxes [B,N,4], areas [B,N],
     masks, is_crowd [B,N], image_ids: host values). With the batch's tensors on the device, as
     the trainer delivers them, a step uploads nothing and never waits for the stream: the keep
@@ -194,6 +319,7 @@ class PoseEvalStep:
         self.kp_weights = joints_mse_keypoint_weights()
         self._state = None                # (counter, rec_kpts, rec_meta), allocated at the first batch
         self.last = None                  # the last batch's device outputs (loss, per_kp, coords, scores)
+        self.last_eval = None             # compute()'s device tensors
         self.reset()
 
     def reset(self):
@@ -258,6 +384,29 @@ class PoseEvalStep:
         self._max_records += sum(keep) * N
         self.last = out
         return out["loss"][0]
+
+    def compute(self, gt: CocoKeypointGT) -> dict:
+        """on_validation_epoch_end's metrics (module.py:600-622) of the epoch's records against
+        ``gt``: COCOeval's evaluate / accumulate / summarize on the device. One small upload (the
+        slots' rows in ``gt``) and one read (the ten numbers and the record counter).
+        ``self.last_eval`` keeps the device tensors (precision, recall, oks, dt_bits, ...)."""
+        K = len(self.kp_weights)
+        if gt.K != K:
+            raise ValueError(f"PoseEvalStep.compute: the annotations have {gt.K} keypoints, the records {K}")
+        if self._state is None:
+            dev = torch.device(self.device)
+            counter, kpts, meta = None, torch.empty(0, K, 3, device=dev), torch.empty(0, 8, device=dev)
+        else:
+            counter, kpts, meta = self._state
+        n = min(self._max_records, kpts.shape[0])
+        ev = coco_keypoint_eval(kpts, meta, counter, n, self._slot_ids, gt)
+        tail = ev["stats"] if counter is None else torch.cat([ev["stats"], counter.view(torch.float64)])
+        host = tail.cpu().numpy()
+        count = 0 if counter is None else int(host[10:].view(np.int64)[0])
+        if count > self.capacity:
+            raise RuntimeError(f"PoseEvalStep: {count} records exceed the capacity {self.capacity}")
+        self.last_eval = ev
+        return dict(zip(COCO_KP_STAT_KEYS, host[:10].tolist()))
 
     def predictions(self) -> list[dict]:
         """The epoch's eval_predictions (module.py:552-561), one device-to-host read."""

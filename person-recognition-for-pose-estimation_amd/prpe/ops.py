@@ -448,6 +448,106 @@ def pose_coco_records(coords, scores, boxes, areas, masks, is_crowd, keep, keypo
                                        cap, _stream()), "prpe_pose_coco_records")
 
 
+# ------------------------------------------------------------------ COCO keypoint AP / AR (csrc/cocoeval.hip)
+COCO_MAX_DETS, COCO_MAX_GT, COCO_IOU_THRS, COCO_REC_THRS, COCO_AREAS = 20, 64, 10, 101, 3
+COCO_EMPTY_BIT = 63
+
+
+def _host_doubles(what, name, v, n):
+    v = [float(x) for x in v]
+    if len(v) != n:
+        raise ValueError(f"{what}: {name} needs {n} values, got {len(v)}")
+    return (C.c_double * n)(*v)
+
+
+def coco_kp_match(rec_kpts, rec_meta, counter, n_max, slot_to_img, gt_start, gt_kpts, gt_bbox, gt_area, gt_iscrowd,
+                  gt_ignore, max_gt, sigmas, iou_thrs, area_rngs, *, want_oks=True, out=None):
+    """COCOeval.evaluate() for keypoints on the device records (prpe_coco_kp_match, include/prpe.h).
+    rec_kpts [cap,K,3] / rec_meta [cap,8] / counter int64 [1] (or None) as ``pose_coco_records``
+    leaves them, ``n_max`` the host's bound on the records; slot_to_img int32 [slots]; the
+    ground-truth table gt_start int32 [I+1], gt_kpts float64 [G,K,3], gt_bbox [G,4], gt_area [G],
+    gt_iscrowd / gt_ignore uint8 [G], ``max_gt`` its largest image (host). Returns a dict of device
+    tensors: dt_score float32 [I,20], dt_bits int64 [I,20], dt_rec int32 [I,20], npig int32 [I,3]
+    and oks float64 [I,20,64]. ``out`` supplies them instead (all four, plus oks if wanted)."""
+    what = "coco_kp_match"
+    _check_dev(what, "gt_start", gt_start, torch.int32, min_numel=2)
+    I = gt_start.numel() - 1
+    dev = gt_start.device
+    _check_dev(what, "rec_kpts", rec_kpts, torch.float32)
+    if rec_kpts.dim() != 3 or rec_kpts.shape[2] != 3:
+        raise ValueError(f"{what}: rec_kpts must be [cap, K, 3], got {list(rec_kpts.shape)}")
+    cap, K = rec_kpts.shape[0], rec_kpts.shape[1]
+    _check_dev(what, "rec_meta", rec_meta, torch.float32, (cap, 8))
+    n_max = int(n_max)
+    if n_max > cap:
+        raise ValueError(f"{what}: n_max {n_max} exceeds the record arrays' capacity {cap}")
+    if counter is not None:
+        _check_dev(what, "counter", counter, torch.int64, (1,))
+    _check_dev(what, "slot_to_img", slot_to_img, torch.int32)
+    _check_dev(what, "gt_kpts", gt_kpts, torch.float64)
+    if gt_kpts.dim() != 3 or tuple(gt_kpts.shape[1:]) != (K, 3):
+        raise ValueError(f"{what}: gt_kpts must be [G, {K}, 3], got {list(gt_kpts.shape)}")
+    G = gt_kpts.shape[0]
+    _check_dev(what, "gt_bbox", gt_bbox, torch.float64, (G, 4))
+    _check_dev(what, "gt_area", gt_area, torch.float64, (G,))
+    _check_dev(what, "gt_iscrowd", gt_iscrowd, torch.uint8, (G,))
+    _check_dev(what, "gt_ignore", gt_ignore, torch.uint8, (G,))
+    sg = _host_doubles(what, "sigmas", sigmas, K)
+    it = _host_doubles(what, "iou_thrs", iou_thrs, COCO_IOU_THRS)
+    ar = _host_doubles(what, "area_rngs", [v for r in area_rngs for v in r], 2 * COCO_AREAS)
+    if out is None:
+        out = {"dt_score": torch.empty(I, COCO_MAX_DETS, device=dev),
+               "dt_bits": torch.empty(I, COCO_MAX_DETS, device=dev, dtype=torch.int64),
+               "dt_rec": torch.empty(I, COCO_MAX_DETS, device=dev, dtype=torch.int32),
+               "npig": torch.empty(I, COCO_AREAS, device=dev, dtype=torch.int32)}
+        if want_oks:
+            out["oks"] = torch.empty(I, COCO_MAX_DETS, COCO_MAX_GT, device=dev, dtype=torch.float64)
+    _check_dev(what, "dt_score", out["dt_score"], torch.float32, (I, COCO_MAX_DETS))
+    _check_dev(what, "dt_bits", out["dt_bits"], torch.int64, (I, COCO_MAX_DETS))
+    _check_dev(what, "dt_rec", out["dt_rec"], torch.int32, (I, COCO_MAX_DETS))
+    _check_dev(what, "npig", out["npig"], torch.int32, (I, COCO_AREAS))
+    if out.get("oks") is not None:
+        _check_dev(what, "oks", out["oks"], torch.float64, (I, COCO_MAX_DETS, COCO_MAX_GT))
+    nbytes = lib().prpe_coco_kp_match_workspace_bytes(I)
+    ws = torch.empty(max(1, (nbytes + 3) // 4), device=dev, dtype=torch.int32)
+    check(lib().prpe_coco_kp_match(rec_kpts.data_ptr(), rec_meta.data_ptr(), _ptr(counter), n_max,
+                                   slot_to_img.data_ptr(), slot_to_img.numel(), gt_start.data_ptr(),
+                                   gt_kpts.data_ptr(), gt_bbox.data_ptr(), gt_area.data_ptr(), gt_iscrowd.data_ptr(),
+                                   gt_ignore.data_ptr(), I, G, int(max_gt), K, sg, it, ar, out["dt_score"].data_ptr(),
+                                   out["dt_bits"].data_ptr(), out["dt_rec"].data_ptr(), out["npig"].data_ptr(),
+                                   _ptr(out.get("oks")), ws.data_ptr(), nbytes, _stream()), "prpe_coco_kp_match")
+    return out
+
+
+def coco_kp_accumulate(dt_score, dt_bits, npig, rec_thrs, *, out=None):
+    """COCOeval.accumulate() and summarize() for keypoints (prpe_coco_kp_accumulate) on
+    ``coco_kp_match``'s tables. Returns device float64 tensors: precision [10,101,3], recall
+    [10,3], stats [10] = AP, AP50, AP75, APm, APl, AR, AR50, AR75, ARm, ARl."""
+    what = "coco_kp_accumulate"
+    _check_dev(what, "dt_score", dt_score, torch.float32)
+    if dt_score.dim() != 2 or dt_score.shape[0] < 1 or dt_score.shape[1] != COCO_MAX_DETS:
+        raise ValueError(f"{what}: dt_score must be [I >= 1, {COCO_MAX_DETS}], got {list(dt_score.shape)}")
+    I = dt_score.shape[0]
+    dev = dt_score.device
+    _check_dev(what, "dt_bits", dt_bits, torch.int64, (I, COCO_MAX_DETS))
+    _check_dev(what, "npig", npig, torch.int32, (I, COCO_AREAS))
+    rt = _host_doubles(what, "rec_thrs", rec_thrs, COCO_REC_THRS)
+    if out is None:
+        out = {"precision": torch.empty(COCO_IOU_THRS, COCO_REC_THRS, COCO_AREAS, device=dev, dtype=torch.float64),
+               "recall": torch.empty(COCO_IOU_THRS, COCO_AREAS, device=dev, dtype=torch.float64),
+               "stats": torch.empty(10, device=dev, dtype=torch.float64)}
+    _check_dev(what, "precision", out["precision"], torch.float64, (COCO_IOU_THRS, COCO_REC_THRS, COCO_AREAS))
+    _check_dev(what, "recall", out["recall"], torch.float64, (COCO_IOU_THRS, COCO_AREAS))
+    _check_dev(what, "stats", out["stats"], torch.float64, (10,))
+    nbytes = lib().prpe_coco_kp_accumulate_workspace_bytes(I)
+    ws = torch.empty(max(1, (nbytes + 7) // 8), device=dev, dtype=torch.int64)
+    check(lib().prpe_coco_kp_accumulate(dt_score.data_ptr(), dt_bits.data_ptr(), npig.data_ptr(), I, rt,
+                                        out["precision"].data_ptr(), out["recall"].data_ptr(),
+                                        out["stats"].data_ptr(), ws.data_ptr(), nbytes, _stream()),
+          "prpe_coco_kp_accumulate")
+    return out
+
+
 # ------------------------------------------------------------------ top-down pose (csrc/topdown.hip)
 CROP_META_COLS = 8
 CROP_BORDER = 2                      # the patch conv's padding = the crop buffer's zero border
