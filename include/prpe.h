@@ -661,6 +661,61 @@ int prpe_face_person_match(const float* crop_meta_p, const int32_t* n_p, int32_t
                            void* stream);
 
 /*
+ * Face crops registered to the skeleton (csrc/facealign.hip). The face branch's
+ * training images are 112 x 112 faces placed by a similarity transform on the ArcFace landmark
+ * positions; the face detector gives no landmarks, the skeleton gives the nose and both eyes.
+ *
+ * face_align_fit: one thread per person slot s < min(*n_p, max_p). Inputs: the face list
+ *   crop_meta_f [max_f][8] and n_f [1], keypoints [max_p][K][3] = (x, y, score) in frame pixels,
+ *   person_face [max_p] int32 = prpe_face_person_match's face_slot. Output: warp [max_f][8], zeroed
+ *   by the caller (stream-ordered); the call writes only the rows it flags. The match is
+ *   one-to-one, so a row has one writer.
+ *   warp row: [0] int32 flag (0: use the window of crop_meta; 1: aligned), [1] int32 person slot,
+ *   [2..7] = a, b, tx, c, d, ty, the map from the centre of output pixel (i, j) to frame pixels
+ *     x = a*(j+0.5) + b*(i+0.5) + tx,   y = c*(j+0.5) + d*(i+0.5) + ty
+ *   (pixel k covers [k, k+1), as roi_resize).
+ *   The fit, all in fp64 without fused operations: template points q_0..2 = (38.2946, 51.6963),
+ *   (73.5318, 51.5014), (56.0252, 71.7366), x times out_w/112 and y times out_h/112 (the factor
+ *   formed first), paired with keypoints 2, 1, 0 (COCO right eye, left eye, nose: the subject's
+ *   right eye is the viewer's left) = p_0..2. Means (v_0 + v_1 + v_2) / 3; with the centred points
+ *   u_i = q_i - mean q, v_i = p_i - mean p, summed in ascending i from 0:
+ *     D = sum (u.x*u.x + u.y*u.y), A = sum (u.x*v.x + u.y*v.y) / D, C = sum (u.x*v.y - u.y*v.x) / D,
+ *     TX = mean p.x - (A*mean q.x - C*mean q.y), TY = mean p.y - (C*mean q.x + A*mean q.y);
+ *   a = d = (float)A, c = (float)C, b = (float)(-C), tx = (float)TX, ty = (float)TY. This is the
+ *   least-squares similarity without reflection from template to frame.
+ *   The row of face f = person_face[s] is written only when all of these hold, else it stays zero:
+ *   0 <= f < min(*n_f, max_f); the three keypoints have score >= kp_thr and finite x, y; the stored
+ *   coefficients are finite; the crop's width in frame pixels
+ *     size = (float)(sqrt(a*a + c*c) * out_w)         (fp64 on the stored a, c, rounded once)
+ *   satisfies scale_lo * w_f <= size <= scale_hi * w_f (exact products in fp64, w_f the face
+ *   window's width, both ends inclusive); and the image of the output centre
+ *     cx = (float)((a*(out_w/2) + b*(out_h/2)) + tx), cy = (float)((c*(out_w/2) + d*(out_h/2)) + ty)
+ *   (fp64 on the stored values, rounded once) lies in the face window: x0 <= cx <= x0 + w_f,
+ *   y0 <= cy <= y0 + h_f (fp32 sums, inclusive).
+ * -EINVAL, nothing launched: a null pointer, max_f, max_p, out_h or out_w below 1, an output side
+ *   above 4096, K < 3, a NaN kp_thr, scale_lo not in (0, scale_hi].
+ *
+ * roi_warp / roi_warp_u8: roi_resize / roi_resize_u8 with warp [max_crops][8] (device). A slot
+ *   whose warp flag is not 1 is resampled from its window exactly as roi_resize does it (the same
+ *   statements: the same bits). A slot with flag 1 samples the frame crop_meta[s] names at
+ *     sx = (a*(j+0.5) + tx) + b*(i+0.5) - 0.5,   sy = (c*(j+0.5) + ty) + d*(i+0.5) - 0.5
+ *   in fp64 from the fp32 coefficients, then as roi_resize: each clamped to [-2, size+1] (NaN
+ *   becomes -2), floor, one fp32 rounding per weight, the two fp32 lerps, taps outside the frame 0
+ *   and never loaded. Empty slots, channel 3, y_amax, a, b and swap_rb: as roi_resize(_u8). The
+ *   launch is roi_resize's: one 128-thread workgroup per (slot, 8 output rows).
+ * -EINVAL, nothing launched: a null warp, and whatever roi_resize(_u8) refuses.
+ */
+int prpe_face_align_fit(const float* crop_meta_f, const int32_t* n_f, int32_t max_f, const int32_t* n_p,
+                        int32_t max_p, const float* keypoints, int32_t K, const int32_t* person_face,
+                        int32_t out_h, int32_t out_w, float kp_thr, float scale_lo, float scale_hi, float* warp,
+                        void* stream);
+int prpe_roi_warp(const prpe_view* frames, const float* crop_meta, const int32_t* n_crops, int32_t max_crops,
+                  const float* warp, const prpe_view* y, float* y_amax /* optional */, void* stream);
+int prpe_roi_warp_u8(const prpe_view_u8* frames, const float* crop_meta, const int32_t* n_crops, int32_t max_crops,
+                     const float* warp, const float* a, const float* b, int32_t swap_rb, const prpe_view* y,
+                     float* y_amax /* optional */, void* stream);
+
+/*
  * Tracking: persons associated across frames, so that a skeleton keeps its track id and the name
  * once read from its face (csrc/track.hip). The reference has no tracker; the
  * semantics are this project's, after the greedy IoU / OKS trackers of top-down pose demos, with

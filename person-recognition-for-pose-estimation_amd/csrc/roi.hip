@@ -15,15 +15,12 @@
 //   one-to-one assignment by a wave-wide minimum of (cost, person, face) keys. No workspace, no
 //   atomics.
 #pragma clang fp contract(off)
-#include <type_traits>
 #include "roi.h"
 
 namespace {
 
 using namespace roi;
 
-constexpr int RR_THREADS = 128;
-constexpr int RR_ROWS = 8;                     // output rows per workgroup
 constexpr int MATCH_MAX = 32;                  // persons / faces per frame the match takes
 
 __global__ __launch_bounds__(SEL_THREADS) void roi_select_kernel(SelK p) {
@@ -81,66 +78,11 @@ __global__ __launch_bounds__(SEL_THREADS) void roi_select_kernel(SelK p) {
 }
 
 template <typename T>
-struct ResK {
-  const T* src; int B, H, W; int64_t sn, sh, sw, sc;
-  const float* meta; const int* n_crops; int max_crops;
-  float* y; int oh, ow; int64_t ysn, ysh, ysw;   // float elements, each a multiple of 4
-  float a[3], b[3];                              // uint8 frames only
-  int swap_rb;
-  float* y_amax;
-};
-
-template <typename T>
 __global__ __launch_bounds__(RR_THREADS) void roi_resize_kernel(ResK<T> p) {
-  constexpr bool U8 = std::is_same<T, uint8_t>::value;
   __shared__ float wmax[RR_THREADS / 64];
-  const int bps = (p.oh + RR_ROWS - 1) / RR_ROWS;               // workgroups per slot
-  const int slot = blockIdx.x / bps, i0 = (blockIdx.x - slot * bps) * RR_ROWS;
-  const int rows = p.oh - i0 < RR_ROWS ? p.oh - i0 : RR_ROWS;
-  float* ybase = p.y + (int64_t)slot * p.ysn + (int64_t)i0 * p.ysh;
-  int n = *p.n_crops;
-  n = n < p.max_crops ? n : p.max_crops;
-  const float* m = p.meta + (int64_t)slot * 8;
-  const int f = slot < n ? __float_as_int(m[0]) : -1;
-  if ((unsigned)f >= (unsigned)p.B) {              // empty slot (or a frame index that is none): zeros
-    for (int j = threadIdx.x; j < p.ow; j += RR_THREADS)
-      for (int r = 0; r < rows; ++r)
-        *reinterpret_cast<f32x4*>(ybase + (int64_t)r * p.ysh + (int64_t)j * p.ysw) = f32x4{0.f, 0.f, 0.f, 0.f};
-    return;                                        // the whole workgroup: y_amax stays as it is
-  }
-  const double x0 = m[2], y0 = m[3], w = m[4], h = m[5];
-  const T* base = p.src + (int64_t)f * p.sn;
-  int64_t oc[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) oc[c] = (int64_t)(U8 && p.swap_rb ? 2 - c : c) * p.sc;
-  float mx = 0.f;
-  for (int j = threadIdx.x; j < p.ow; j += RR_THREADS) {
-    const Tap tx = tap(x0, w, j, p.ow, p.W);
-    const int64_t oa = (int64_t)(tx.ina ? tx.ia : 0) * p.sw, ob = (int64_t)(tx.inb ? tx.ib : 0) * p.sw;
-    float* yo = ybase + (int64_t)j * p.ysw;
-#pragma unroll 4
-    for (int r = 0; r < rows; ++r) {
-      const Tap ty = tap(y0, h, i0 + r, p.oh, p.H);
-      const T* ra = base + (int64_t)(ty.ina ? ty.ia : 0) * p.sh;
-      const T* rb = base + (int64_t)(ty.inb ? ty.ib : 0) * p.sh;
-      float v[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        v[c] = blend(ra + oc[c], rb + oc[c], oa, ob, tx, ty);
-        if constexpr (U8) v[c] = v[c] * p.a[c] + p.b[c];
-        mx = fmaxf(mx, fabsf(v[c]));
-      }
-      *reinterpret_cast<f32x4*>(yo + (int64_t)r * p.ysh) = f32x4{v[0], v[1], v[2], 0.f};
-    }
-  }
-  if (!p.y_amax) return;
-  mx = warp_max(mx);
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    mx = fmaxf(wmax[0], wmax[1]);
-    if (mx > 0.f) atomicMax(reinterpret_cast<unsigned*>(p.y_amax + slot), __float_as_uint(mx));
-  }
+  ResBlock k;
+  if (!resize_block(p, k)) return;
+  resize_amax(p, k.slot, resize_window(p, k), wmax);
 }
 
 struct MatchK {
@@ -268,19 +210,8 @@ __global__ __launch_bounds__(64) void face_person_match_kernel(MatchK p) {
   }
 }
 
-bool y_ok(const prpe_view* y, int32_t max_crops) {
-  return view_ok(y) && y->n == max_crops && y->c == 4 && y->sc == 1 && y->sw % 4 == 0 && y->sh % 4 == 0 &&
-         y->sn % 4 == 0 && (uintptr_t)y->ptr % 16 == 0 && y->h <= MAX_OUT && y->w <= MAX_OUT;
-}
-
 template <typename T>
-int roi_resize_launch(ResK<T>& p, const prpe_view* y, const float* crop_meta, const int32_t* n_crops,
-                      int32_t max_crops, float* y_amax, void* stream) {
-  const int64_t blocks = (int64_t)max_crops * ((y->h + RR_ROWS - 1) / RR_ROWS);
-  if (blocks >= (1LL << 31)) return PRPE_EINVAL;
-  p.meta = crop_meta; p.n_crops = n_crops; p.max_crops = max_crops;
-  p.y = y->ptr; p.oh = y->h; p.ow = y->w; p.ysn = y->sn; p.ysh = y->sh; p.ysw = y->sw;
-  p.y_amax = y_amax;
+int roi_resize_launch(const ResK<T>& p, int64_t blocks, void* stream) {
   hipLaunchKernelGGL(roi_resize_kernel<T>, dim3((unsigned)blocks), dim3(RR_THREADS), 0, as_stream(stream), p);
   return launch_status();
 }
@@ -311,29 +242,21 @@ extern "C" int prpe_roi_select(const float* dets, const int32_t* counts, int32_t
 
 extern "C" int prpe_roi_resize(const prpe_view* frames, const float* crop_meta, const int32_t* n_crops,
                                int32_t max_crops, const prpe_view* y, float* y_amax, void* stream) {
-  if (!frames || !frames->ptr || !crop_meta || !n_crops) return PRPE_EINVAL;
-  if (frames->c != 3 || frames->n <= 0 || frames->h <= 0 || frames->w <= 0) return PRPE_EINVAL;
-  if (frames->h > MAX_DIM || frames->w > MAX_DIM) return PRPE_EINVAL;
-  if (max_crops <= 0 || !y_ok(y, max_crops)) return PRPE_EINVAL;
   ResK<float> p{};
-  p.src = frames->ptr; p.B = frames->n; p.H = frames->h; p.W = frames->w;
-  p.sn = frames->sn; p.sh = frames->sh; p.sw = frames->sw; p.sc = frames->sc;
-  return roi_resize_launch(p, y, crop_meta, n_crops, max_crops, y_amax, stream);
+  int64_t blocks;
+  if (!resize_args(p, frames, crop_meta, n_crops, max_crops, y, y_amax, blocks)) return PRPE_EINVAL;
+  return roi_resize_launch(p, blocks, stream);
 }
 
 extern "C" int prpe_roi_resize_u8(const prpe_view_u8* frames, const float* crop_meta, const int32_t* n_crops,
                                   int32_t max_crops, const float* a, const float* b, int32_t swap_rb,
                                   const prpe_view* y, float* y_amax, void* stream) {
-  if (!frames || !frames->ptr || !crop_meta || !n_crops || !a || !b) return PRPE_EINVAL;
-  if (frames->c != 3 || frames->n <= 0 || frames->h <= 0 || frames->w <= 0) return PRPE_EINVAL;
-  if (frames->h > MAX_DIM || frames->w > MAX_DIM) return PRPE_EINVAL;
-  if (max_crops <= 0 || !y_ok(y, max_crops)) return PRPE_EINVAL;
   ResK<uint8_t> p{};
-  p.src = frames->ptr; p.B = frames->n; p.H = frames->h; p.W = frames->w;
-  p.sn = frames->sn; p.sh = frames->sh; p.sw = frames->sw; p.sc = frames->sc;
+  int64_t blocks;
+  if (!a || !b || !resize_args(p, frames, crop_meta, n_crops, max_crops, y, y_amax, blocks)) return PRPE_EINVAL;
   for (int c = 0; c < 3; ++c) { p.a[c] = a[c]; p.b[c] = b[c]; }
   p.swap_rb = swap_rb ? 1 : 0;
-  return roi_resize_launch(p, y, crop_meta, n_crops, max_crops, y_amax, stream);
+  return roi_resize_launch(p, blocks, stream);
 }
 
 extern "C" int prpe_face_person_match(const float* crop_meta_p, const int32_t* n_p, int32_t max_p,

@@ -111,6 +111,9 @@ SIGNATURES = {
     "prpe_roi_resize": (C.c_int, [_VP, _P, _P, _I, _VP, _P, _P]),
     "prpe_roi_resize_u8": (C.c_int, [_VP, _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _VP, _P, _P]),
     "prpe_face_person_match": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P]),
+    "prpe_face_align_fit": (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P]),
+    "prpe_roi_warp": (C.c_int, [_VP, _P, _P, _I, _P, _VP, _P, _P]),
+    "prpe_roi_warp_u8": (C.c_int, [_VP, _P, _P, _I, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _VP, _P, _P]),
     "prpe_track_update": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _F, _I, C.POINTER(C.c_float), _F, _I,
                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "prpe_coco_kp_match_workspace_bytes": (C.c_int64, [_I]),

@@ -831,6 +831,72 @@ def face_person_match(crop_meta_p, n_p, keypoints, crop_meta_f, n_f, ident, scor
     return face_slot, person_ident, person_score, status
 
 
+# ------------------------------------------------------------------ aligned face crops (csrc/facealign.hip)
+WARP_COLS = 8                        # flag, person slot, a, b, tx, c, d, ty
+
+
+def face_align_fit(crop_meta_f, n_f, n_p, keypoints, person_face, out_hw, *, warp, kp_thr=0.3, scale=(0.5, 2.0)):
+    """The similarity that puts each matched person's eyes and nose (keypoints [P, K, 3] in frame
+    pixels; COCO 2, 1, 0) on the ArcFace template of an ``out_hw`` crop -> ``warp`` [F, 8], the
+    face list's rows for prpe_roi_warp (prpe_face_align_fit, include/prpe.h). ``person_face`` [P]
+    int32 is ``face_person_match``'s face_slot; ``warp`` must be zeroed by the caller: only the
+    rows that pass the gates (``kp_thr``, ``scale`` = (lo, hi) of crop width over window width, the
+    crop centre inside the window) are written. No host read."""
+    what = "prpe_face_align_fit"
+    if not (isinstance(crop_meta_f, torch.Tensor) and crop_meta_f.dim() == 2):
+        raise ValueError(f"{what}: crop_meta_f must be [F, {CROP_META_COLS}]")
+    if not (isinstance(keypoints, torch.Tensor) and keypoints.dim() == 3 and keypoints.shape[2] == 3):
+        raise ValueError(f"{what}: keypoints must be [P, K, 3]")
+    F, (P, K, _) = crop_meta_f.shape[0], keypoints.shape
+    _check_dev(what, "crop_meta_f", crop_meta_f, torch.float32, (F, CROP_META_COLS))
+    _check_dev(what, "n_f", n_f, torch.int32, (1,))
+    _check_dev(what, "n_p", n_p, torch.int32, (1,))
+    _check_dev(what, "keypoints", keypoints, torch.float32, (P, K, 3))
+    _check_dev(what, "person_face", person_face, torch.int32, (P,))
+    _check_dev(what, "warp", warp, torch.float32, (F, WARP_COLS))
+    oh, ow = (int(v) for v in out_hw)
+    lo, hi = (float(v) for v in scale)
+    kp_thr = float(kp_thr)
+    if P < 1 or F < 1 or K < 3 or kp_thr != kp_thr or not 0.0 < lo <= hi:
+        raise ValueError(f"{what}: P = {P}, F = {F}, K = {K} (at least 3), kp_thr = {kp_thr}, scale = {(lo, hi)} "
+                         f"(0 < lo <= hi)")
+    if not (1 <= oh <= ROI_MAX_OUT and 1 <= ow <= ROI_MAX_OUT):
+        raise ValueError(f"{what}: the output size {(oh, ow)} must be within 1..{ROI_MAX_OUT}")
+    check(lib().prpe_face_align_fit(crop_meta_f.data_ptr(), n_f.data_ptr(), F, n_p.data_ptr(), P, keypoints.data_ptr(),
+                                    K, person_face.data_ptr(), oh, ow, kp_thr, lo, hi, warp.data_ptr(), _stream()),
+          what)
+    return warp
+
+
+def roi_warp(frames, crop_meta, n_crops, warp, y, y_amax=None):
+    """``roi_resize`` with ``warp`` [max_crops, 8] (``face_align_fit``'s): a slot whose row is
+    flagged is sampled along the row's affine map, every other slot from its window with
+    ``roi_resize``'s bits (prpe_roi_warp, include/prpe.h)."""
+    what = "prpe_roi_warp"
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.float32 and
+            frames.dim() == 4 and frames.shape[1] == 3 and frames.numel() > 0):
+        raise ValueError(f"{what}: frames must be a float32 device tensor [B, 3, H, W]")
+    max_crops = _roi_args(what, crop_meta, n_crops, y, y_amax)
+    _check_dev(what, "warp", warp, torch.float32, (max_crops, WARP_COLS))
+    check(lib().prpe_roi_warp(C.byref(view(nhwc(frames))), crop_meta.data_ptr(), n_crops.data_ptr(), max_crops,
+                              warp.data_ptr(), C.byref(view(y)), _ptr(y_amax), _stream()), what)
+    return y
+
+
+def roi_warp_u8(frames, crop_meta, n_crops, warp, y, a=(1.0, 1.0, 1.0), b=(0.0, 0.0, 0.0), swap_rb=False,
+                y_amax=None):
+    """``roi_warp`` from uint8 source frames [B, Hs, Ws, 3] (any strides) with ``roi_resize_u8``'s
+    a, b and channel order (prpe_roi_warp_u8, include/prpe.h)."""
+    what = "prpe_roi_warp_u8"
+    fv = _u8_frames(what, frames)
+    max_crops = _roi_args(what, crop_meta, n_crops, y, y_amax)
+    _check_dev(what, "warp", warp, torch.float32, (max_crops, WARP_COLS))
+    check(lib().prpe_roi_warp_u8(C.byref(fv), crop_meta.data_ptr(), n_crops.data_ptr(), max_crops, warp.data_ptr(),
+                                 _f3(what, "a", a), _f3(what, "b", b), int(bool(swap_rb)), C.byref(view(y)),
+                                 _ptr(y_amax), _stream()), what)
+    return y
+
+
 # ------------------------------------------------------------------ tracking across frames (csrc/track.hip)
 TRACK_SLOTS = 32                     # track slots per stream, and persons per frame track_update takes
 TRACK_MAX_K = 64                     # keypoints per person
