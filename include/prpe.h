@@ -858,6 +858,45 @@ int prpe_coco_kp_accumulate(const float* dt_score, const uint64_t* dt_bits, cons
                             const double* rec_thrs /* HOST */, double* precision, double* recall, double* stats,
                             void* workspace, int64_t workspace_bytes, void* stream);
 
+/*
+ * 1:1 face verification: the scores of all pairs between two sets of enrolled rows, binned into a
+ * genuine and an impostor histogram (csrc/pairhist.hip). The score matrix never
+ * reaches memory. The reference has no verification code; the semantics are this project's.
+ * The library allocates nothing; no host sync. Additive to ABI 12.
+ *
+ * Operands: a [M][D] and b [N][D], fp32 rows that are ALREADY L2-normalised -- prpe_gallery_enrol's
+ *   output, what a gallery stores. Nothing is normalised here (normalising twice is not
+ *   bit-idempotent), so a score is the one prpe_gallery_topk compares. Row strides in elements,
+ *   >= D and a multiple of 4; a and b 16-byte aligned. D is a multiple of 32 in [32, 512].
+ *   a_labels [M] / b_labels [N] int64; a_valid [M] / b_valid [N] optional bytes.
+ * Modes: b == NULL is self mode: the pairs (i, j), i < j, of a (b_labels and b_valid must be NULL
+ *   too; b_row_stride and N are ignored). Only the upper triangle of score tiles is computed.
+ *   Otherwise cross mode: all M x N pairs (a[i], b[j]).
+ * score(i, j) = (a0 + a1) + (a2 + a3), a_e the chain acc = fma(x[c], y[c], acc) over the columns c
+ *   with c % 4 == e in ascending order: the same bits prpe_gallery_topk gives for those two
+ *   normalised rows, whatever the position of the pair, M, N or the mode; score(i, j) == score(j, i).
+ * Which pairs count: a row with label < 0 or valid byte 0 takes part in no pair. A pair is genuine
+ *   when the two labels are equal, else impostor. A pair whose score is not finite (a NaN or
+ *   infinite element on either side) adds 1 to skipped[0] and to no bin.
+ * Bins: nbins in {256, 512, 1024, 2048, 4096}, h = nbins / 2,
+ *   bin(s) = clamp((int)floorf(s * h) + h, 0, nbins - 1); s * h is exact (h is a power of two; it
+ *   is a product and a floor, never fmaf(s, h, h), which would round a tiny negative score up).
+ *   With edge_b = (b - h) / h (exact in fp32): for b in 1..nbins-1, s >= edge_b <=> bin(s) >= b, so
+ *   the impostor count in bins >= b is exactly the number of pairs an identify at
+ *   threshold = edge_b accepts.
+ * Output: hist uint64 [2][nbins] (row 0 genuine, row 1 impostor) and skipped uint64 [1] are ADDED
+ *   to (64-bit atomic adds), not overwritten: the caller zeroes them, and may chunk a large set or
+ *   add several sets into one histogram. Integer adds commute: two runs give the same numbers.
+ * -EINVAL, nothing launched and nothing written: a null a, a_labels, hist or skipped; b_labels or
+ *   b_valid without b; b without b_labels; M (or, with b, N) below 1 or above 2^24; D not a
+ *   multiple of 32 in [32, 512]; nbins outside the list; a row stride below D or not a multiple of
+ *   4; a or b not 16-byte aligned. M = 1 in self mode is legal and counts nothing.
+ */
+int prpe_pair_hist(const float* a, int64_t a_row_stride, int32_t M, const int64_t* a_labels,
+                   const uint8_t* a_valid /* optional */, const float* b /* NULL: self mode */,
+                   int64_t b_row_stride, int32_t N, const int64_t* b_labels, const uint8_t* b_valid /* optional */,
+                   int32_t D, int32_t nbins, uint64_t* hist, uint64_t* skipped, void* stream);
+
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse
  * a library built from other sources than the ones beside it. */

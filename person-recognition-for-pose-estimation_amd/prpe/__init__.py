@@ -16,9 +16,10 @@ from .model import CombinedModel, PoseOutput  # noqa: F401
 from .postproc import keypoints_from_heatmaps, non_max_suppression, non_max_suppression_padded  # noqa: F401
 from .topdown import TopDownPose  # noqa: F401
 from .tracks import PersonTracker  # noqa: F401
+from .verification import FaceVerification  # noqa: F401
 
 __all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "CocoKeypointGT", "coco_keypoint_eval",
-           "TopDownPose", "FrameIngest", "FaceGallery", "FaceIdentifier",
+           "TopDownPose", "FrameIngest", "FaceGallery", "FaceIdentifier", "FaceVerification",
            "FaceCrops", "PersonRecognition", "PersonTracker",
            "non_max_suppression",
            "non_max_suppression_padded", "keypoints_from_heatmaps", "state_dict_spec", "TASKS"]

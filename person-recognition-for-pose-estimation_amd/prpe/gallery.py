@@ -6,7 +6,8 @@
   ``remove`` clears valid bytes with elementwise device ops, ``search`` is the fused cosine top-k,
   ``identify`` the top-1 with a rejection threshold. No call synchronises with the host.
 * ``FaceIdentifier`` — frames -> trunk -> AdaFace embedding -> ``add`` / ``identify``; it calls the
-  engine directly, so the model's ``set_task`` state is left alone.
+  engine directly, so the model's ``set_task`` state is left alone. ``calibrate`` takes its
+  threshold from a ``FaceVerification`` (prpe/verification.py) at a target FAR.
 
 The reference names the task (scripts/modify_models.py:331) but has no gallery code; the semantics
 are stated in include/prpe.h.
@@ -136,6 +137,14 @@ class FaceIdentifier:
 
     def __call__(self, frames):
         return self.gallery.identify(self.embed(frames), self.threshold)
+
+    def calibrate(self, verification, far: float):
+        """Set ``threshold`` to the lowest bin edge at which the impostor pairs of ``verification``
+        (a ``prpe.FaceVerification``) are accepted at a rate of at most ``far``; returns that row of
+        ``verification.compute`` (threshold, tar, false_accepts, true_accepts). One host read."""
+        row = verification.compute(far=(far,))["at_far"][0]
+        self.threshold = float(row["threshold"])
+        return row
 
     def from_frames_u8(self, frames_u8, ingest=None):
         """``__call__`` on uint8 source frames [B, Hs, Ws, 3] through ``trunk_u8`` (prpe.FrameIngest)."""

@@ -1050,3 +1050,61 @@ def gallery_topk(queries, gallery, G, k, *, scores, rows, valid=None, labels=Non
                                   scores.data_ptr(), rows.data_ptr(), _ptr(labels), float(threshold), _ptr(ident),
                                   workspace.data_ptr(), workspace.numel(), _stream()), what)
     return scores, rows
+
+
+# ------------------------------------------------------------------ face verification (csrc/pairhist.hip)
+PAIR_HIST_TILE = 128                 # rows and columns of the score tile a workgroup takes
+PAIR_HIST_BINS = (256, 512, 1024, 2048, 4096)
+PAIR_HIST_MAX_ROWS = 1 << 24
+
+
+def _pair_rows(what, name, t, D):
+    """``t`` [n, D] float32 on the device, unit column stride, row stride >= D and a multiple of 4,
+    16-byte aligned; returns (n, row stride)."""
+    ok = (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and
+          t.shape[1] == D and 1 <= t.shape[0] <= PAIR_HIST_MAX_ROWS)
+    if ok:
+        ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), D)
+        ok = t.stride(1) == 1 and ld >= D and ld % 4 == 0 and t.data_ptr() % 16 == 0
+    if not ok:
+        got = (type(t).__name__ if not isinstance(t, torch.Tensor) else
+               f"{t.dtype} {list(t.shape)} strides {list(t.stride())} on {t.device}")
+        raise ValueError(f"{what}: {name} must be a float32 device tensor [1..2^24, {D}] with unit column stride, a "
+                         f"row stride >= {D} that is a multiple of 4 and a 16-byte aligned start, got {got}")
+    return t.shape[0], ld
+
+
+def pair_hist(a, a_labels, b=None, b_labels=None, *, nbins, hist, skipped, a_valid=None, b_valid=None):
+    """Scores of all pairs of already normalised rows (``gallery_enrol``'s output), binned
+    (prpe_pair_hist, include/prpe.h). ``b`` None: the pairs i < j of ``a`` [M, D]; else all pairs of
+    ``a`` and ``b`` [N, D]. Labels int64 [M] / [N]; a row with a negative label or a zero byte in
+    ``a_valid`` / ``b_valid`` (uint8, optional) takes part in no pair. ``hist`` int64 [2, nbins]
+    (row 0 genuine, row 1 impostor) and ``skipped`` int64 [1] (pairs whose score is not finite) are
+    ADDED to: the caller zeroes them. No host read."""
+    what = "prpe_pair_hist"
+    if not (isinstance(a, torch.Tensor) and a.dim() == 2):
+        raise ValueError(f"{what}: a must be [M, D]")
+    D = a.shape[1]
+    _gallery_dim(what, D)
+    nbins = int(nbins)
+    if nbins not in PAIR_HIST_BINS:
+        raise ValueError(f"{what}: nbins must be one of {PAIR_HIST_BINS}, got {nbins}")
+    M, lda = _pair_rows(what, "a", a, D)
+    _check_dev(what, "a_labels", a_labels, torch.int64, (M,))
+    if a_valid is not None:
+        _check_dev(what, "a_valid", a_valid, torch.uint8, (M,))
+    N, ldb = 0, 0
+    if b is None:
+        if b_labels is not None or b_valid is not None:
+            raise ValueError(f"{what}: b_labels and b_valid need b")
+    else:
+        N, ldb = _pair_rows(what, "b", b, D)
+        _check_dev(what, "b_labels", b_labels, torch.int64, (N,))
+        if b_valid is not None:
+            _check_dev(what, "b_valid", b_valid, torch.uint8, (N,))
+    _check_dev(what, "hist", hist, torch.int64, (2, nbins))
+    _check_dev(what, "skipped", skipped, torch.int64, (1,))
+    check(lib().prpe_pair_hist(a.data_ptr(), lda, M, a_labels.data_ptr(), _ptr(a_valid), _ptr(b), ldb, N,
+                               _ptr(b_labels), _ptr(b_valid), D, nbins, hist.data_ptr(), skipped.data_ptr(),
+                               _stream()), what)
+    return hist, skipped
