@@ -897,6 +897,73 @@ int prpe_pair_hist(const float* a, int64_t a_row_stride, int32_t M, const int64_
                    int64_t b_row_stride, int32_t N, const int64_t* b_labels, const uint8_t* b_valid /* optional */,
                    int32_t D, int32_t nbins, uint64_t* hist, uint64_t* skipped, void* stream);
 
+/*
+ * Clustering of unlabelled face embeddings: DBSCAN over cosine similarity on enrolled rows, self
+ * mode (csrc/facecluster.hip). prpe_pair_hist's GEMM with another epilogue: the
+ * score matrix never reaches memory. The reference has no clustering code; the semantics are this
+ * project's. The library allocates nothing; no host sync. Additive to ABI 12.
+ *
+ * Operands: a [N][D], fp32 rows that are ALREADY L2-normalised (prpe_gallery_enrol's output;
+ *   nothing is normalised here). Row stride in elements, >= D and a multiple of 4; a 16-byte
+ *   aligned; D a multiple of 32 in [32, 512]; 1 <= N <= 2^24, as for prpe_pair_hist. valid [N]:
+ *   optional bytes; a row with valid byte 0 takes part in nothing. Labels play no role.
+ * score(i, j): prpe_pair_hist's and prpe_gallery_topk's bits, (a0 + a1) + (a2 + a3), a_e the chain
+ *   acc = fma(x[c], y[c], acc) over the columns c with c % 4 == e in ascending order.
+ * Neighbours: i and j are neighbours when i != j, both rows take part, the score is finite and
+ *   score(i, j) >= threshold (fp32 compare; equality accepts, as prpe_gallery_topk's ident does).
+ *   A NaN or infinite score is no neighbour and is counted nowhere.
+ * degree[i]: the number of neighbours of i (0 for a row that takes no part). A row is CORE when
+ *   degree[i] + 1 >= min_samples (the row counts itself). With min_samples == 1 every row that
+ *   takes part is core and the clusters are the connected components (single linkage).
+ * Clusters: two core rows that are neighbours are in one cluster, transitively.
+ * Border: a row that takes part, is not core and has at least one core neighbour joins the cluster
+ *   of the core neighbour with the highest score, the lowest row on ties. (Textbook DBSCAN leaves
+ *   this to visiting order; here two runs must agree.) Every other row that takes part is noise.
+ * Outputs, all caller-allocated device memory:
+ *   root [N] int32: the lowest core row of the row's cluster; -1 for noise and left-out rows.
+ *   kind [N] uint8: 0 left out, 1 noise, 2 border, 3 core.
+ *   degree [N] int32.
+ *   cluster [N] int32: compact ids 0 .. C-1, ascending with the cluster's root; -1 where root is.
+ *   n_clusters [1] int32: the true C, also when it exceeds max_clusters.
+ *   sizes [max_clusters] int32: core and border members per cluster.
+ *   sums [max_clusters][D] int64: per cluster and column the sum over its members of
+ *     llrintf(a[i][d] * 2^32) (the product is exact). Integer adds commute: the sums equal a host
+ *     sum exactly on every run; |element| <= 1 and N <= 2^24 bound a sum by 2^56. The sums of a
+ *     cluster that holds a NaN or infinite element are unspecified.
+ *   centroids [max_clusters][D] fp32: (float)((double)sums * 2^-32), not normalised.
+ *   Clusters with id >= max_clusters keep their ids in cluster but get no size, sum or centroid;
+ *   the rows of sizes, sums and centroids past min(C, max_clusters) are left untouched.
+ * Every output is a function of the inputs alone: two runs, any grid and any tile order give the
+ *   same bits.
+ * Stages (each needs the previous one's outputs, in stream order):
+ *   prpe_pair_degree  overwrites degree.
+ *   prpe_pair_link    initialises the workspace (best [N] uint64, then parent [N] int32; at least
+ *     prpe_face_cluster_workspace_bytes(N) bytes, 256-byte aligned) and links: the core rows of a
+ *     cluster end under one root in a union-find (parent[x] <= x, hooks by compare-and-swap, the
+ *     root the lowest core row), a border candidate's best core neighbour in
+ *     best = image(score) << 32 | (0xFFFFFFFF - row), image the order-preserving uint32 of the score.
+ *   prpe_cluster_finish  reads degree and the workspace; writes root, kind, cluster, n_clusters and
+ *     sizes[0 .. min(C, max_clusters)).
+ *   prpe_cluster_centroids  reads cluster and n_clusters; writes sums and centroids
+ *     [0 .. min(C, max_clusters)).
+ * -EINVAL, nothing launched and nothing written: what prpe_pair_hist refuses of a, its stride, N
+ *   and D; min_samples < 1; a threshold that is not finite; max_clusters < 1; a null degree or
+ *   output; a workspace that is null, too small or not 256-byte aligned.
+ *   prpe_face_cluster_workspace_bytes returns -EINVAL for N outside [1, 2^24].
+ */
+int64_t prpe_face_cluster_workspace_bytes(int32_t N);
+int prpe_pair_degree(const float* a, int64_t a_row_stride, int32_t N, const uint8_t* valid /* optional */, int32_t D,
+                     float threshold, int32_t* degree, void* stream);
+int prpe_pair_link(const float* a, int64_t a_row_stride, int32_t N, const uint8_t* valid /* optional */, int32_t D,
+                   float threshold, int32_t min_samples, const int32_t* degree, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+int prpe_cluster_finish(int32_t N, const uint8_t* valid /* optional */, int32_t min_samples, const int32_t* degree,
+                        const void* workspace, int64_t workspace_bytes, int32_t* root, uint8_t* kind,
+                        int32_t* cluster, int32_t* n_clusters, int32_t max_clusters, int32_t* sizes, void* stream);
+int prpe_cluster_centroids(const float* a, int64_t a_row_stride, int32_t N, int32_t D, const int32_t* cluster,
+                           const int32_t* n_clusters, int32_t max_clusters, int64_t* sums, float* centroids,
+                           void* stream);
+
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse
  * a library built from other sources than the ones beside it. */

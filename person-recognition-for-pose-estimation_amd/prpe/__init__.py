@@ -8,6 +8,7 @@ Device work: hand-written HIP kernels in ../csrc behind the C ABI of include/prp
 torch.distributed (RCCL) only.
 """
 from .arch import TASKS, state_dict_spec  # noqa: F401
+from .clusters import FaceClustering, FaceClusters  # noqa: F401
 from .evalsteps import CocoKeypointGT, PoseEvalStep, coco_keypoint_eval  # noqa: F401
 from .faces import FaceCrops, PersonRecognition  # noqa: F401
 from .gallery import FaceGallery, FaceIdentifier  # noqa: F401
@@ -20,6 +21,6 @@ from .verification import FaceVerification  # noqa: F401
 
 __all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "CocoKeypointGT", "coco_keypoint_eval",
            "TopDownPose", "FrameIngest", "FaceGallery", "FaceIdentifier", "FaceVerification",
-           "FaceCrops", "PersonRecognition", "PersonTracker",
+           "FaceClusters", "FaceClustering", "FaceCrops", "PersonRecognition", "PersonTracker",
            "non_max_suppression",
            "non_max_suppression_padded", "keypoints_from_heatmaps", "state_dict_spec", "TASKS"]

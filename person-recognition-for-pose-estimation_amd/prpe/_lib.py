@@ -108,6 +108,11 @@ SIGNATURES = {
     "prpe_gallery_topk_workspace_bytes": (C.c_int64, [_I, _I, _I]),
     "prpe_gallery_topk": (C.c_int, [_P, _L, _I, _I, _P, _I, _P, _I, _P, _P, _P, _F, _P, _P, _L, _P]),
     "prpe_pair_hist": (C.c_int, [_P, _L, _I, _P, _P, _P, _L, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "prpe_face_cluster_workspace_bytes": (C.c_int64, [_I]),
+    "prpe_pair_degree": (C.c_int, [_P, _L, _I, _P, _I, _F, _P, _P]),
+    "prpe_pair_link": (C.c_int, [_P, _L, _I, _P, _I, _F, _I, _P, _P, _L, _P]),
+    "prpe_cluster_finish": (C.c_int, [_I, _P, _I, _P, _P, _L, _P, _P, _P, _P, _I, _P, _P]),
+    "prpe_cluster_centroids": (C.c_int, [_P, _L, _I, _I, _P, _P, _I, _P, _P, _P]),
     "prpe_roi_select": (C.c_int, [_P, _P, _I, _I, _F, _I, _F, _F, _F, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P]),
     "prpe_roi_resize": (C.c_int, [_VP, _P, _P, _I, _VP, _P, _P]),
     "prpe_roi_resize_u8": (C.c_int, [_VP, _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _VP, _P, _P]),

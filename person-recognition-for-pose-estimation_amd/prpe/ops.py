@@ -8,6 +8,7 @@ residuals with stride 0 ...); the source frames of ``frame_ingest`` / ``crop_res
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -1108,3 +1109,107 @@ def pair_hist(a, a_labels, b=None, b_labels=None, *, nbins, hist, skipped, a_val
                                _ptr(b_labels), _ptr(b_valid), D, nbins, hist.data_ptr(), skipped.data_ptr(),
                                _stream()), what)
     return hist, skipped
+
+
+# ------------------------------------------------------------------ face clustering (csrc/facecluster.hip)
+def face_cluster_workspace_bytes(N):
+    """Bytes of the workspace ``pair_link`` and ``cluster_finish`` share for ``N`` rows
+    (prpe_face_cluster_workspace_bytes: best [N] uint64, parent [N] int32)."""
+    nbytes = lib().prpe_face_cluster_workspace_bytes(int(N))
+    if nbytes < 0:
+        raise ValueError(f"prpe_face_cluster_workspace_bytes({N}) failed")
+    return nbytes
+
+
+def _cluster_rows(what, a, valid):
+    if not (isinstance(a, torch.Tensor) and a.dim() == 2):
+        raise ValueError(f"{what}: a must be [N, D]")
+    D = a.shape[1]
+    _gallery_dim(what, D)
+    N, lda = _pair_rows(what, "a", a, D)
+    if valid is not None:
+        _check_dev(what, "valid", valid, torch.uint8, (N,))
+    return N, D, lda
+
+
+def _cluster_threshold(what, threshold, min_samples=1):
+    threshold, min_samples = float(threshold), int(min_samples)
+    if not math.isfinite(threshold) or min_samples < 1:
+        raise ValueError(f"{what}: the threshold must be finite and min_samples >= 1, got {threshold}, {min_samples}")
+    return threshold, min_samples
+
+
+def _cluster_workspace(what, workspace, N):
+    _check_dev(what, "workspace", workspace, torch.uint8, min_numel=face_cluster_workspace_bytes(N))
+    if workspace.data_ptr() % 256:
+        raise ValueError(f"{what}: the workspace must be 256-byte aligned")
+
+
+def pair_degree(a, threshold, *, degree, valid=None):
+    """Pass 1 of the clustering (prpe_pair_degree, include/prpe.h): ``degree`` [N] int32 is
+    overwritten with every row's number of neighbours among the already normalised rows ``a``
+    [N, D] at ``threshold``. ``valid`` [N] uint8, optional: 0 leaves the row out. No host read."""
+    what = "prpe_pair_degree"
+    N, D, lda = _cluster_rows(what, a, valid)
+    threshold, _ = _cluster_threshold(what, threshold)
+    _check_dev(what, "degree", degree, torch.int32, (N,))
+    check(lib().prpe_pair_degree(a.data_ptr(), lda, N, _ptr(valid), D, threshold, degree.data_ptr(), _stream()), what)
+    return degree
+
+
+def pair_link(a, threshold, min_samples, *, degree, workspace, valid=None):
+    """Pass 2 (prpe_pair_link): with ``degree`` from ``pair_degree`` at the same threshold, links
+    the core rows of a cluster under one root and records every other row's best core neighbour,
+    in ``workspace`` (uint8, >= face_cluster_workspace_bytes(N), 256-byte aligned). No host read."""
+    what = "prpe_pair_link"
+    N, D, lda = _cluster_rows(what, a, valid)
+    threshold, min_samples = _cluster_threshold(what, threshold, min_samples)
+    _check_dev(what, "degree", degree, torch.int32, (N,))
+    _cluster_workspace(what, workspace, N)
+    check(lib().prpe_pair_link(a.data_ptr(), lda, N, _ptr(valid), D, threshold, min_samples, degree.data_ptr(),
+                               workspace.data_ptr(), workspace.numel(), _stream()), what)
+    return workspace
+
+
+def cluster_finish(N, min_samples, *, degree, workspace, root, kind, cluster, n_clusters, sizes, valid=None):
+    """Flatten, classify and compact (prpe_cluster_finish): fills root [N] int32, kind [N] uint8
+    (0 left out, 1 noise, 2 border, 3 core), cluster [N] int32, n_clusters [1] int32 and
+    sizes[0 .. min(C, max_clusters)) with max_clusters = sizes.numel(). No host read."""
+    what = "prpe_cluster_finish"
+    N = int(N)
+    _, min_samples = _cluster_threshold(what, 0.0, min_samples)
+    if not 1 <= N <= PAIR_HIST_MAX_ROWS:
+        raise ValueError(f"{what}: N must lie in [1, 2^24], got {N}")
+    if valid is not None:
+        _check_dev(what, "valid", valid, torch.uint8, (N,))
+    _check_dev(what, "degree", degree, torch.int32, (N,))
+    _cluster_workspace(what, workspace, N)
+    _check_dev(what, "root", root, torch.int32, (N,))
+    _check_dev(what, "kind", kind, torch.uint8, (N,))
+    _check_dev(what, "cluster", cluster, torch.int32, (N,))
+    _check_dev(what, "n_clusters", n_clusters, torch.int32, (1,))
+    _check_dev(what, "sizes", sizes, torch.int32, min_numel=1)
+    if sizes.dim() != 1:
+        raise ValueError(f"{what}: sizes must be [max_clusters]")
+    check(lib().prpe_cluster_finish(N, _ptr(valid), min_samples, degree.data_ptr(), workspace.data_ptr(),
+                                    workspace.numel(), root.data_ptr(), kind.data_ptr(), cluster.data_ptr(),
+                                    n_clusters.data_ptr(), sizes.numel(), sizes.data_ptr(), _stream()), what)
+    return root, kind, cluster, n_clusters, sizes
+
+
+def cluster_centroids(a, *, cluster, n_clusters, sums, centroids):
+    """Per-cluster fixed-point sums and centroids (prpe_cluster_centroids): sums [max_clusters, D]
+    int64 and centroids [max_clusters, D] float32 (not normalised), rows [0, min(C, max_clusters))
+    written, the others left as they are. No host read."""
+    what = "prpe_cluster_centroids"
+    N, D, lda = _cluster_rows(what, a, None)
+    _check_dev(what, "cluster", cluster, torch.int32, (N,))
+    _check_dev(what, "n_clusters", n_clusters, torch.int32, (1,))
+    if not (isinstance(sums, torch.Tensor) and sums.dim() == 2 and sums.shape[0] >= 1):
+        raise ValueError(f"{what}: sums must be [max_clusters >= 1, D]")
+    max_clusters = sums.shape[0]
+    _check_dev(what, "sums", sums, torch.int64, (max_clusters, D))
+    _check_dev(what, "centroids", centroids, torch.float32, (max_clusters, D))
+    check(lib().prpe_cluster_centroids(a.data_ptr(), lda, N, D, cluster.data_ptr(), n_clusters.data_ptr(), max_clusters,
+                                       sums.data_ptr(), centroids.data_ptr(), _stream()), what)
+    return sums, centroids
