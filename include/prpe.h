@@ -583,6 +583,40 @@ int prpe_gallery_topk(const float* queries, int64_t q_row_stride, int32_t Q, int
                       int64_t workspace_bytes, void* stream);
 
 /*
+ * The same search for many queries per call (csrc/gallery_wide.hip): a bf16
+ * matrix-core pass over the gallery keeps, per query, a set of rows that provably contains the
+ * exact top-k; those rows are scored with prpe_gallery_topk's fp32 chain, and a query whose set
+ * cannot be proven sufficient is finished by prpe_gallery_topk's own kernels, on the device.
+ *
+ * Operands, storage and refusals are prpe_gallery_topk's (the gallery is the same fp32 rows: no
+ * second copy, no change to enrolment). scores, rows and ident receive the bits prpe_gallery_topk
+ * writes for the same call: the order, the skipped non-finite scores, valid, the (-inf, -1) tail
+ * and ident's >= threshold included.
+ * Premise of that equality: gallery rows [0, G) are prpe_gallery_enrol's output, unit or zero rows
+ *   (norm at most 1 up to fp32 rounding) -- what the storage holds by definition. Rows and queries
+ *   with NaN or infinite elements are handled as prpe_gallery_topk handles them (skipped).
+ * PRPE_GALLERY_WIDE_EPS(D): for such rows, |coarse - exact| <= eps, coarse the bf16 pass's score
+ *   and exact the fp32 chain's. With u = 2^-8 the unit roundoff of bf16 round-to-nearest, rounding
+ *   both operands moves the real dot product by at most (2u + u^2) |q||g| = 2^-7 + 2^-16
+ *   (Cauchy-Schwarz); the fp32 accumulation of the coarse sum (products of two bf16 are exact in
+ *   fp32; one ulp, 2^-23, allowed per addition of the matrix core's adder) and of the exact chain
+ *   (2^-24 per fma) add less than 3.05 D 2^-24; D 2^-22 covers that, the rounding of the stored
+ *   norms and of the bar itself. DESIGN.md 5k has the derivation and the sufficiency argument.
+ * route (optional) [Q] bytes: 0 = the filter's certificate held for the query, 1 = the exact
+ *   kernels produced its rows.
+ * workspace: >= prpe_gallery_topk_wide_workspace_bytes(Q, G, k) bytes, 256-byte aligned; nothing
+ *   is allocated, nothing read back, no atomics: two runs give the same bytes. Concurrent calls on
+ *   different streams must pass different workspaces.
+ * -EINVAL, nothing launched: prpe_gallery_topk's conditions, with this workspace size.
+ */
+#define PRPE_GALLERY_WIDE_EPS(D) (0.0078125 + 0.0000152587890625 + (double)(D) * (1.0 / 4194304.0))
+int64_t prpe_gallery_topk_wide_workspace_bytes(int32_t Q, int32_t G, int32_t k);
+int prpe_gallery_topk_wide(const float* queries, int64_t q_row_stride, int32_t Q, int32_t D, const float* gallery,
+                           int32_t G, const uint8_t* valid, int32_t k, float* scores, int32_t* rows,
+                           const int64_t* labels, float threshold, int64_t* ident, uint8_t* route, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
+/*
  * Per-face identification: face boxes -> 112 x 112 crops in the stem's buffer -> the trunk ->
  * AdaFace -> the gallery, and the join of identities to skeletons (csrc/roi.hip).
  * The reference trains its face branch on 112 x 112 face images through the shared trunk

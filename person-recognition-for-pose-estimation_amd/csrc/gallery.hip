@@ -23,31 +23,22 @@
 //   acc = fma(g[c], q[c], acc) over the columns c with c % 4 == e in ascending order (one MFMA per
 //   16-column step and e, summing c = 16 st + 4 j + e over j = 0..3), whatever tile, wave, chunk
 //   or query block the pair lands in.
+// The wide route (gallery_wide.hip) reuses launch 0 with a bf16 copy of the queries
+// and, for the queries its filter cannot certify, launches 1 and 2 in their LIST variants.
 #pragma clang fp contract(off)
-#include "common.h"
+#include "gallery.h"
+
+#include <type_traits>
 
 namespace {
 
-constexpr int GL_NW = 4;            // waves per workgroup
-constexpr int GL_TILE = 16;         // gallery rows per wave step (one MFMA tile)
-constexpr int GL_STEP_ROWS = GL_NW * GL_TILE;
-constexpr int GL_KMAX = 8;
-constexpr int GL_DMAX = 512;
-constexpr int GL_PF = 8;            // 16-column steps per register buffer (128 columns)
-constexpr int GL_EMPTY = 0x7fffffff;   // row of an empty slot inside the kernels (-1 in the output)
-constexpr float GL_EPS = 1e-12f;    // F.normalize
-
-struct Ent { float s; int r; };
-
-__device__ __forceinline__ bool gl_finite(float v) { return fabsf(v) <= 3.402823466e38f; }   // false for NaN
-// the total order: score descending, then row ascending
-__device__ __forceinline__ bool gl_better(float s, int r, float s2, int r2) { return s > s2 || (s == s2 && r < r2); }
-
 // ------------------------------------------------------------------------- normalise (enrol, queries)
 // prpe_l2norm's arithmetic: the squares summed in fp64 (lane-strided, then across the wave),
-// norm = (float) sqrt, y = x / max(norm, eps) as an fp32 division
+// norm = (float) sqrt, y = x / max(norm, eps) as an fp32 division. BF16 (the wide route's queries,
+// DESIGN.md 5k): ybf receives the same values rounded to nearest even
+template <bool BF16>
 __global__ __launch_bounds__(256) void gallery_normalise_kernel(const float* x, int64_t ldx, int n, int D, float* y,
-                                                                float* norm) {
+                                                                float* norm, __bf16* ybf) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n) return;
   const int lane = threadIdx.x & 63;
@@ -56,52 +47,12 @@ __global__ __launch_bounds__(256) void gallery_normalise_kernel(const float* x, 
   for (int c = lane; c < D; c += 64) s += (double)xr[c] * xr[c];
   const float nrm = (float)sqrt(warp_sum_d(s));
   const float den = fmaxf(nrm, GL_EPS);
-  for (int c = lane; c < D; c += 64) y[(int64_t)row * D + c] = xr[c] / den;
+  for (int c = lane; c < D; c += 64) {
+    const float v = xr[c] / den;
+    y[(int64_t)row * D + c] = v;
+    if constexpr (BF16) ybf[(int64_t)row * D + c] = (__bf16)v;
+  }
   if (norm && lane == 0) norm[row] = nrm;
-}
-
-// ------------------------------------------------------------------------- wave-wide selection
-// a lane's sorted list of up to 8 entries, in registers (every index static)
-struct Local {
-  float s[GL_KMAX];
-  int r[GL_KMAX];
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int j = 0; j < GL_KMAX; ++j) { s[j] = -INFINITY; r[j] = GL_EMPTY; }
-  }
-  __device__ __forceinline__ void push(float es, int er) {
-    if (!gl_better(es, er, s[GL_KMAX - 1], r[GL_KMAX - 1])) return;
-    s[GL_KMAX - 1] = es;
-    r[GL_KMAX - 1] = er;
-#pragma unroll
-    for (int j = GL_KMAX - 1; j > 0; --j) {
-      if (gl_better(s[j], r[j], s[j - 1], r[j - 1])) {
-        const float ts = s[j]; s[j] = s[j - 1]; s[j - 1] = ts;
-        const int tr = r[j]; r[j] = r[j - 1]; r[j - 1] = tr;
-      }
-    }
-  }
-  __device__ __forceinline__ void pop() {
-#pragma unroll
-    for (int j = 0; j < GL_KMAX - 1; ++j) { s[j] = s[j + 1]; r[j] = r[j + 1]; }
-    s[GL_KMAX - 1] = -INFINITY;
-    r[GL_KMAX - 1] = GL_EMPTY;
-  }
-};
-
-// the best head of the wave's 64 local lists, removed from its list; every lane returns it.
-// Rows are unique across the lists (empty slots apart), so exactly one lane pops.
-__device__ __forceinline__ Ent wave_take_best(Local& loc) {
-  float bs = loc.s[0];
-  int br = loc.r[0];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float os = __shfl_xor(bs, o, 64);
-    const int orow = __shfl_xor(br, o, 64);
-    if (gl_better(os, orow, bs, br)) { bs = os; br = orow; }
-  }
-  if (br != GL_EMPTY && loc.r[0] == br) loc.pop();
-  return Ent{bs, br};
 }
 
 // ------------------------------------------------------------------------- phase 1
@@ -112,9 +63,15 @@ struct TopkK {
   Ent* part;              // [nchunks][Q][k]
   int Q, D, G, k, chunk, nqb;
 };
+// LIST (the wide route's fallback): the queries are list[0 .. *count), ascending
+// indices into qn, whose rows are normalised already; the lists go to part[..][list[i]][..]
+struct TopkKL : TopkK {
+  const int* list;
+  const int* count;
+};
 
-template <int QT, bool FULL>
-__global__ __launch_bounds__(GL_NW * 64) void gallery_topk_kernel(TopkK p) {
+template <int QT, bool FULL, bool LIST = false>
+__global__ __launch_bounds__(GL_NW * 64) void gallery_topk_kernel(std::conditional_t<LIST, TopkKL, TopkK> p) {
   constexpr int QB = QT * 16;
   constexpr int QS_BYTES = QB * GL_DMAX * 4;
   __shared__ __attribute__((aligned(16))) unsigned char lds[QS_BYTES + GL_NW * QB * GL_KMAX * (int)sizeof(Ent)];
@@ -123,8 +80,15 @@ __global__ __launch_bounds__(GL_NW * 64) void gallery_topk_kernel(TopkK p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, g = lane >> 4;
-  const int qb0 = ((int)blockIdx.x % p.nqb) * QB;
   const int c = (int)blockIdx.x / p.nqb;
+  // LIST: the few live query blocks are the first ones; rotated by the chunk, their workgroups
+  // spread over all XCDs (workgroup i runs on XCD i % 8) instead of piling onto one
+  const int qb0 = (LIST ? ((int)blockIdx.x % p.nqb + c) % p.nqb : (int)blockIdx.x % p.nqb) * QB;
+  int nq = p.Q;   // queries of this launch
+  if constexpr (LIST) {
+    nq = *p.count;
+    if (qb0 >= nq) return;
+  }
   const int D = p.D, G = p.G, k = p.k;
   const int nsteps = D >> 4;
 
@@ -133,9 +97,12 @@ __global__ __launch_bounds__(GL_NW * 64) void gallery_topk_kernel(TopkK p) {
   const int d4 = D >> 2;
   for (int i = tid; i < QB * d4; i += GL_NW * 64) {
     const int ql = i / d4, col = (i - ql * d4) * 4;
-    const int q = qb0 + ql;
+    int q = qb0 + ql;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (q < p.Q) v = *reinterpret_cast<const f32x4*>(p.qn + (int64_t)q * D + col);
+    if (q < nq) {
+      if constexpr (LIST) q = p.list[q];
+      v = *reinterpret_cast<const f32x4*>(p.qn + (int64_t)q * D + col);
+    }
     const int t = ql >> 4, st = col >> 4, gg = (col >> 2) & 3;
     *reinterpret_cast<f32x4*>(qs + ((t * nsteps + st) * 64 + gg * 16 + (ql & 15)) * 4) = v;
   }
@@ -232,8 +199,9 @@ __global__ __launch_bounds__(GL_NW * 64) void gallery_topk_kernel(TopkK p) {
 
   // the chunk's list of query ql: the best k of the waves' lists
   for (int ql = wave; ql < QB; ql += GL_NW) {
-    const int q = qb0 + ql;
-    if (q >= p.Q) break;
+    int q = qb0 + ql;
+    if (q >= nq) break;
+    if constexpr (LIST) q = p.list[q];
     Local loc;
     loc.clear();
     if (lane < GL_NW * k) {
@@ -255,8 +223,19 @@ struct MergeK {
   const int64_t* labels; float threshold; int64_t* ident;
 };
 
-__global__ __launch_bounds__(64) void gallery_merge_kernel(MergeK p) {
-  const int q = blockIdx.x, lane = threadIdx.x;
+struct MergeKL : MergeK {
+  const int* list;
+  const int* count;
+};
+
+template <bool LIST = false>
+__global__ __launch_bounds__(64) void gallery_merge_kernel(std::conditional_t<LIST, MergeKL, MergeK> p) {
+  int q = blockIdx.x;
+  const int lane = threadIdx.x;
+  if constexpr (LIST) {
+    if (q >= *p.count) return;
+    q = p.list[q];
+  }
   const int k = p.k;
   Local loc;
   loc.clear();
@@ -277,26 +256,6 @@ __global__ __launch_bounds__(64) void gallery_merge_kernel(MergeK p) {
   }
 }
 
-// ------------------------------------------------------------------------- host
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-inline bool dim_ok(int D) { return D >= 32 && D <= GL_DMAX && D % 32 == 0; }
-constexpr int GL_GMAX = 0x7fffffff - 4096;
-
-// query block width, query blocks, rows per chunk (a multiple of 64) and chunks: enough
-// workgroups to fill the chip a few times over, each with a long contiguous walk at large G
-struct Plan { int qb, nqb, chunk, nchunks; };
-inline Plan gallery_plan(int Q, int G) {
-  Plan pl;
-  pl.qb = Q <= 16 ? 16 : 64;
-  pl.nqb = (Q + pl.qb - 1) / pl.qb;
-  const int tiles = (G + GL_STEP_ROWS - 1) / GL_STEP_ROWS;
-  const int target = Q <= 16 ? 1024 : (512 / pl.nqb > 1 ? 512 / pl.nqb : 1);
-  const int tpc = (tiles + target - 1) / target;
-  pl.chunk = tpc * GL_STEP_ROWS;
-  pl.nchunks = (tiles + tpc - 1) / tpc;
-  return pl;
-}
-
 }  // namespace
 
 extern "C" int prpe_gallery_enrol(const float* x, int64_t x_row_stride, int32_t n, int32_t D, float* gallery,
@@ -304,8 +263,8 @@ extern "C" int prpe_gallery_enrol(const float* x, int64_t x_row_stride, int32_t 
   if (!x || !gallery || !norms || n < 1 || !dim_ok(D) || capacity < 1 || row0 < 0 ||
       (int64_t)row0 + n > capacity || x_row_stride < D || ((uintptr_t)gallery & 15))
     return PRPE_EINVAL;
-  hipLaunchKernelGGL(gallery_normalise_kernel, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), x, x_row_stride,
-                     n, D, gallery + (int64_t)row0 * D, norms + row0);
+  hipLaunchKernelGGL(gallery_normalise_kernel<false>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), x,
+                     x_row_stride, n, D, gallery + (int64_t)row0 * D, norms + row0, static_cast<__bf16*>(nullptr));
   return launch_status();
 }
 
@@ -330,8 +289,8 @@ extern "C" int prpe_gallery_topk(const float* queries, int64_t q_row_stride, int
   float* qn = static_cast<float*>(workspace);
   Ent* part = reinterpret_cast<Ent*>(static_cast<unsigned char*>(workspace) + align256((int64_t)Q * GL_DMAX * 4));
 
-  hipLaunchKernelGGL(gallery_normalise_kernel, dim3((Q + 3) / 4), dim3(256), 0, st, queries, q_row_stride, Q, D, qn,
-                     static_cast<float*>(nullptr));
+  hipLaunchKernelGGL(gallery_normalise_kernel<false>, dim3((Q + 3) / 4), dim3(256), 0, st, queries, q_row_stride, Q,
+                     D, qn, static_cast<float*>(nullptr), static_cast<__bf16*>(nullptr));
   int e = launch_status();
   if (e) return e;
 
@@ -349,6 +308,35 @@ extern "C" int prpe_gallery_topk(const float* queries, int64_t q_row_stride, int
   if (e) return e;
 
   MergeK mk{part, pl.nchunks, Q, k, scores, rows, labels, threshold, ident};
-  hipLaunchKernelGGL(gallery_merge_kernel, dim3(Q), dim3(64), 0, st, mk);
+  hipLaunchKernelGGL(gallery_merge_kernel<false>, dim3(Q), dim3(64), 0, st, mk);
+  return launch_status();
+}
+
+int gallery_launch_normalise_bf16(const float* queries, int64_t q_row_stride, int Q, int D, float* qn, __bf16* qbf,
+                                  hipStream_t st) {
+  hipLaunchKernelGGL(gallery_normalise_kernel<true>, dim3((Q + 3) / 4), dim3(256), 0, st, queries, q_row_stride, Q,
+                     D, qn, static_cast<float*>(nullptr), qbf);
+  return launch_status();
+}
+
+int gallery_launch_listed(const float* qn, int Q, int D, const float* gallery, int G, const uint8_t* valid, int k,
+                          float* scores, int32_t* rows, const int64_t* labels, float threshold, int64_t* ident,
+                          void* part, const int* list, const int* count, hipStream_t st) {
+  const Plan pl = gallery_plan_listed(Q, G);
+  if ((int64_t)pl.nqb * pl.nchunks > 0x7fffffff) return PRPE_EINVAL;
+  TopkKL tk{{qn, gallery, valid, static_cast<Ent*>(part), Q, D, G, k, pl.chunk, pl.nqb}, list, count};
+  const dim3 grid(pl.nqb * pl.nchunks), block(GL_NW * 64);
+  const bool full = D % (GL_PF * 16) == 0;
+  if (pl.qb == 16) {
+    if (full) hipLaunchKernelGGL((gallery_topk_kernel<1, true, true>), grid, block, 0, st, tk);
+    else hipLaunchKernelGGL((gallery_topk_kernel<1, false, true>), grid, block, 0, st, tk);
+  } else {
+    if (full) hipLaunchKernelGGL((gallery_topk_kernel<4, true, true>), grid, block, 0, st, tk);
+    else hipLaunchKernelGGL((gallery_topk_kernel<4, false, true>), grid, block, 0, st, tk);
+  }
+  int e = launch_status();
+  if (e) return e;
+  MergeKL mk{{static_cast<const Ent*>(part), pl.nchunks, Q, k, scores, rows, labels, threshold, ident}, list, count};
+  hipLaunchKernelGGL(gallery_merge_kernel<true>, dim3(Q), dim3(64), 0, st, mk);
   return launch_status();
 }

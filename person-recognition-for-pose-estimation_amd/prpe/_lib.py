@@ -107,6 +107,8 @@ SIGNATURES = {
     "prpe_gallery_enrol": (C.c_int, [_P, _L, _I, _I, _P, _P, _I, _I, _P]),
     "prpe_gallery_topk_workspace_bytes": (C.c_int64, [_I, _I, _I]),
     "prpe_gallery_topk": (C.c_int, [_P, _L, _I, _I, _P, _I, _P, _I, _P, _P, _P, _F, _P, _P, _L, _P]),
+    "prpe_gallery_topk_wide_workspace_bytes": (C.c_int64, [_I, _I, _I]),
+    "prpe_gallery_topk_wide": (C.c_int, [_P, _L, _I, _I, _P, _I, _P, _I, _P, _P, _P, _F, _P, _P, _P, _L, _P]),
     "prpe_pair_hist": (C.c_int, [_P, _L, _I, _P, _P, _P, _L, _I, _P, _P, _I, _I, _P, _P, _P]),
     "prpe_face_cluster_workspace_bytes": (C.c_int64, [_I]),
     "prpe_pair_degree": (C.c_int, [_P, _L, _I, _P, _I, _F, _P, _P]),

@@ -5,6 +5,8 @@
   all on the device. ``add`` appends (the size is a host integer: nothing is read back),
   ``remove`` clears valid bytes with elementwise device ops, ``search`` is the fused cosine top-k,
   ``identify`` the top-1 with a rejection threshold. No call synchronises with the host.
+  ``route`` ("exact", "wide" or "auto") chooses between the exact search and the wide-batch route
+  of DESIGN.md §5k, which returns the same bits and is faster for many queries per call.
 * ``FaceIdentifier`` — frames -> trunk -> AdaFace embedding -> ``add`` / ``identify``; it calls the
   engine directly, so the model's ``set_task`` state is left alone. ``calibrate`` takes its
   threshold from a ``FaceVerification`` (prpe/verification.py) at a target FAR.
@@ -20,8 +22,10 @@ from . import ops
 
 
 class FaceGallery:
-    def __init__(self, dim: int = 512, capacity: int = 4096, device="cuda"):
+    def __init__(self, dim: int = 512, capacity: int = 4096, device="cuda", route: str = "exact"):
         dim, capacity = int(dim), int(capacity)
+        ops.gallery_route(route, 1, 1)
+        self.route = route
         if dim % 32 or not 32 <= dim <= ops.GALLERY_MAX_DIM:
             raise ValueError(f"FaceGallery: dim must be a multiple of 32 in [32, {ops.GALLERY_MAX_DIM}], got {dim}")
         if capacity < 1:
@@ -77,30 +81,38 @@ class FaceGallery:
         if self._size < 1:
             raise ValueError(f"FaceGallery.{what}: the gallery is empty")
 
-    def search(self, embeddings, k: int = 5):
+    def _topk(self, route, Q):
+        """ops.gallery_topk or ops.gallery_topk_wide: ``route`` (None: the gallery's own setting) is
+        "exact", "wide" or "auto" (wide from ops.GALLERY_WIDE_MIN_Q queries and ops.GALLERY_WIDE_MIN_G
+        enrolled rows on). Both give the same bits."""
+        taken = ops.gallery_route(self.route if route is None else route, Q, self._size)
+        return ops.gallery_topk_wide if taken == "wide" else ops.gallery_topk
+
+    def search(self, embeddings, k: int = 5, route=None):
         """(scores [Q, k], rows [Q, k] int32, labels [Q, k] int64): the k best enrolled rows per
         embedding by cosine similarity, descending (ties: the lower row); rows / labels -1 and score
-        -inf where fewer than k rows are valid."""
+        -inf where fewer than k rows are valid. ``route`` overrides the gallery's setting for this call."""
         self._require_rows("search")
         e = self._embeddings("search", embeddings)
         Q = e.shape[0]
         scores = torch.empty(Q, k, device=self.device, dtype=torch.float32)
         rows = torch.empty(Q, k, device=self.device, dtype=torch.int32)
-        ops.gallery_topk(e, self.rows, self._size, k, scores=scores, rows=rows, valid=self.valid)
+        self._topk(route, Q)(e, self.rows, self._size, k, scores=scores, rows=rows, valid=self.valid)
         lab = torch.where(rows >= 0, self.labels[rows.clamp(min=0).long()], torch.full_like(rows, -1, dtype=torch.int64))
         return scores, rows, lab
 
-    def identify(self, embeddings, threshold: float):
+    def identify(self, embeddings, threshold: float, route=None):
         """(ident [Q] int64, score [Q]): the label of the best valid row when its cosine similarity
-        is at least ``threshold``, else -1; score is that best similarity (-inf with no valid row)."""
+        is at least ``threshold``, else -1; score is that best similarity (-inf with no valid row).
+        ``route`` overrides the gallery's setting for this call."""
         self._require_rows("identify")
         e = self._embeddings("identify", embeddings)
         Q = e.shape[0]
         scores = torch.empty(Q, 1, device=self.device, dtype=torch.float32)
         rows = torch.empty(Q, 1, device=self.device, dtype=torch.int32)
         ident = torch.empty(Q, device=self.device, dtype=torch.int64)
-        ops.gallery_topk(e, self.rows, self._size, 1, scores=scores, rows=rows, valid=self.valid, labels=self.labels,
-                         threshold=float(threshold), ident=ident)
+        self._topk(route, Q)(e, self.rows, self._size, 1, scores=scores, rows=rows, valid=self.valid,
+                             labels=self.labels, threshold=float(threshold), ident=ident)
         return ident, scores.view(Q)
 
 

@@ -1018,7 +1018,11 @@ def gallery_topk(queries, gallery, G, k, *, scores, rows, valid=None, labels=Non
     ident[q] = labels[rows[q, 0]] when scores[q, 0] >= threshold, else -1. ``workspace``: a uint8
     device tensor of at least prpe_gallery_topk_workspace_bytes(Q, G, k) bytes (allocated here when
     None). No host read."""
-    what = "prpe_gallery_topk"
+    return _gallery_topk("prpe_gallery_topk", queries, gallery, G, k, scores, rows, valid, labels, threshold, ident,
+                         workspace, None, False)
+
+
+def _gallery_topk(what, queries, gallery, G, k, scores, rows, valid, labels, threshold, ident, workspace, route, wide):
     if not (isinstance(queries, torch.Tensor) and queries.dim() == 2 and isinstance(gallery, torch.Tensor) and
             gallery.dim() == 2):
         raise ValueError(f"{what}: queries must be [Q, D] and gallery [capacity, D]")
@@ -1039,18 +1043,76 @@ def gallery_topk(queries, gallery, G, k, *, scores, rows, valid=None, labels=Non
     if labels is not None:
         _check_dev(what, "labels", labels, torch.int64, min_numel=G)
         _check_dev(what, "ident", ident, torch.int64, (Q,))
-    nbytes = lib().prpe_gallery_topk_workspace_bytes(Q, G, k)
+    if route is not None:
+        _check_dev(what, "route", route, torch.uint8, (Q,))
+    nbytes = getattr(lib(), what + "_workspace_bytes")(Q, G, k)
     if nbytes < 0:
-        raise ValueError(f"{what}: prpe_gallery_topk_workspace_bytes({Q}, {G}, {k}) failed")
+        raise ValueError(f"{what}: {what}_workspace_bytes({Q}, {G}, {k}) failed")
     if workspace is None:
         workspace = torch.empty(nbytes, device=queries.device, dtype=torch.uint8)
     _check_dev(what, "workspace", workspace, torch.uint8, min_numel=nbytes)
     if gallery.data_ptr() % 16 or workspace.data_ptr() % 256:
         raise ValueError(f"{what}: the gallery must be 16-byte and the workspace 256-byte aligned")
-    check(lib().prpe_gallery_topk(queries.data_ptr(), D, Q, D, gallery.data_ptr(), G, _ptr(valid), k,
-                                  scores.data_ptr(), rows.data_ptr(), _ptr(labels), float(threshold), _ptr(ident),
-                                  workspace.data_ptr(), workspace.numel(), _stream()), what)
+    head = (queries.data_ptr(), D, Q, D, gallery.data_ptr(), G, _ptr(valid), k, scores.data_ptr(), rows.data_ptr(),
+            _ptr(labels), float(threshold), _ptr(ident))
+    tail = (workspace.data_ptr(), workspace.numel(), _stream())
+    if wide:
+        check(lib().prpe_gallery_topk_wide(*head, _ptr(route), *tail), what)
+    else:
+        check(lib().prpe_gallery_topk(*head, *tail), what)
     return scores, rows
+
+
+GALLERY_WIDE_QB = 64                 # queries a filter workgroup holds in LDS
+GALLERY_WIDE_L = 8                   # entries of a (chunk, query) list of the filter
+GALLERY_WIDE_C = 64                  # candidates the exact re-score takes per query
+GALLERY_ROUTES = ("exact", "wide", "auto")
+# "auto" takes the wide route for at least this many queries against at least this many rows: at
+# 1 M rows the wide route's slowest run beat the exact route's fastest from Q = 64 on (the smallest
+# such measured Q), at 10 000 rows it lost at every measured Q but one, so no Q serves both sizes
+# and "auto" stays on the exact route below the larger measured size
+GALLERY_WIDE_MIN_Q = 64
+GALLERY_WIDE_MIN_G = 1_000_000
+
+
+def gallery_wide_eps(D):
+    """PRPE_GALLERY_WIDE_EPS(D) of include/prpe.h: the proven bound on |coarse - exact| for unit or
+    zero rows (2^-7 + 2^-16 + D 2^-22)."""
+    return 2.0 ** -7 + 2.0 ** -16 + D * 2.0 ** -22
+
+
+def gallery_wide_plan(Q, G):
+    """(query blocks, rows per chunk, chunks) of the wide route's filter: ``wide_plan`` of
+    csrc/gallery_wide.hip restated. The results never depend on it; tests use it to aim at chunk
+    boundaries and to restate the certificate."""
+    nqb = -(-Q // GALLERY_WIDE_QB)
+    tiles = -(-G // GALLERY_STEP_ROWS)
+    target = max(512 // nqb, 64)
+    tpc = -(-tiles // target)
+    return nqb, tpc * GALLERY_STEP_ROWS, -(-tiles // tpc)
+
+
+def gallery_route(route, Q, G):
+    """The route a search of ``Q`` queries over ``G`` rows takes under the setting ``route``:
+    "exact" or "wide"."""
+    if route not in GALLERY_ROUTES:
+        raise ValueError(f"gallery route must be one of {GALLERY_ROUTES}, got {route!r}")
+    if route == "auto":
+        return "wide" if Q >= GALLERY_WIDE_MIN_Q and G >= GALLERY_WIDE_MIN_G else "exact"
+    return route
+
+
+def gallery_topk_wide(queries, gallery, G, k, *, scores, rows, valid=None, labels=None, threshold=0.0, ident=None,
+                      route=None, workspace=None):
+    """``gallery_topk`` for many queries per call (prpe_gallery_topk_wide, include/prpe.h): the same
+    arguments, the same checks and the same bits in scores, rows and ident. A bf16 filter finds a
+    provably sufficient candidate set per query, the candidates are scored exactly, and a query the
+    filter cannot certify is finished by the exact kernels on the device. ``route`` (optional)
+    [Q] uint8 receives 0 for a certified query and 1 for one the exact kernels finished.
+    ``workspace``: at least prpe_gallery_topk_wide_workspace_bytes(Q, G, k) bytes. The gallery rows
+    must be ``gallery_enrol``'s output. No host read."""
+    return _gallery_topk("prpe_gallery_topk_wide", queries, gallery, G, k, scores, rows, valid, labels, threshold,
+                         ident, workspace, route, True)
 
 
 # ------------------------------------------------------------------ face verification (csrc/pairhist.hip)
