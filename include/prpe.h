@@ -540,6 +540,58 @@ int prpe_crop_resize_u8(const prpe_view_u8* frames, const float* crop_meta, cons
                         void* stream);
 
 /*
+ * frame_ingest_multi (csrc/ingest_multi.hip; additive to ABI 12): prpe_frame_ingest
+ * for a batch whose frames differ in size -- one camera each -- and, with filter = 1, an
+ * antialiased downscale. One source frame and where it lands in the model frame:
+ */
+typedef struct prpe_ingest_src {
+  const uint8_t* ptr;        /* device, logical [h, w, 3] */
+  int32_t h, w;
+  int64_t sh, sw, sc;        /* strides in elements (= bytes) */
+  int32_t top, left, nh, nw; /* its region inside H x W (FrameIngest.geometry) */
+} prpe_ingest_src;
+
+/*
+ * srcs: a HOST array of B frames. It is validated on the host and travels in the kernel arguments,
+ * as a, b and fill do: one launch per chunk of at most 32 frames, no upload, no workspace, no
+ * allocation, and no pointer to srcs is kept once the call returns. y, a, b, fill, swap_rb, y_amax,
+ * the fill outside a frame's region, channel 3 = 0 and the untouched border are prpe_frame_ingest's.
+ *
+ * filter = 0 (bilinear): for each frame n, y[n] and y_amax[n] have the bytes prpe_frame_ingest
+ *   writes for that frame alone with the same region (the arithmetic stated there).
+ * filter = 1 (antialias): separable, per axis; stated for x with scale = Ws / nw in fp64, y alike.
+ *   scale <= 1 (same size, upscaling): the axis keeps prpe_frame_ingest's two taps and weight, bit
+ *   for bit; at nh == Hs and nw == Ws the output still has the bits of torch's u8.float() * a + b.
+ *   scale > 1: torch's triangle filter (F.interpolate(mode="bilinear", align_corners=False,
+ *   antialias=True); the fp64 weights below are aten's to the bit, checked against the torch build
+ *   the tests run on). In fp64:
+ *     centre = scale * (j - left + 0.5)
+ *     xmin = max((int64)(centre - scale + 0.5), 0),  xmax = min((int64)(centre + scale + 0.5), Ws)
+ *     t_k = max(0, 1 - |(k - centre + 0.5) * (1 / scale)|)    for k in [xmin, xmax)
+ *     w_k = (float)(t_k / sum t)          (sum: k ascending from 0.0; rounded to fp32 once)
+ *   Accumulation in fp32, products then adds, never an fma, every sum ascending from 0.f. A sum
+ *   is taken as its first tap plus the weighted differences from it -- prpe_frame_ingest's lerp
+ *   v0 + ax * (v1 - v0) carried to n taps -- so a constant window gives the constant exactly
+ *   (an all-255 frame is 255 * a + b to the bit), whatever the rounded weights sum to:
+ *     h_r = v[r][xmin] + sum_{k > xmin} w_k * (v[r][k] - v[r][xmin])
+ *                                         (two-tap x axis: h_r = v0 + ax * (v1 - v0))
+ *     raw = h_ymin + sum_{r > ymin} wy_r * (h_r - h_ymin)
+ *                                         (two-tap y axis: raw = h_ya + ay * (h_yb - h_ya))
+ *     y[.., c] = raw * a[c] + b[c]        as in prpe_frame_ingest.
+ *   With weights that sum to 1 this is sum_k w_k v_k; the first tap's own weight is never used.
+ *   The order depends on the output pixel alone: a frame's bytes do not depend on B, on its index,
+ *   on the chunk it falls in or on its neighbours.
+ * -EINVAL, nothing launched (no chunk): a null pointer, B < 1, B != y->n, filter outside {0, 1},
+ *   any frame with a null ptr, a side below 1 or above 2^24, or a region that is empty or not inside
+ *   H x W; with filter = 1 a frame with h > 32 * nh or w > 32 * nw (8K into 640 is 12);
+ *   prpe_frame_ingest's conditions on y. No argument makes the kernel read outside a source frame:
+ *   windows are cut to [0, Ws) and two-tap coordinates clamped before they become indices.
+ */
+int prpe_frame_ingest_multi(const prpe_ingest_src* srcs /* HOST array [B] */, int32_t B, const prpe_view* y,
+                            int32_t filter /* 0 bilinear, 1 antialias */, const float* a, const float* b,
+                            const float* fill, int32_t swap_rb, float* y_amax /* optional */, void* stream);
+
+/*
  * Face identification: a gallery of enrolled embeddings and a fused cosine top-k search
  * (csrc/gallery.hip). The reference lists face_identification among its tasks
  * (scripts/modify_models.py:331) but has no gallery code; the semantics are this project's.

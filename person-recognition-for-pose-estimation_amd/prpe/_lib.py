@@ -28,6 +28,13 @@ class View(C.Structure):
                 ("sn", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64), ("sc", C.c_int64)]
 
 
+class IngestSrc(C.Structure):
+    """prpe_ingest_src: one source frame of prpe_frame_ingest_multi and its region in the model frame."""
+    _fields_ = [("ptr", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32),
+                ("sh", C.c_int64), ("sw", C.c_int64), ("sc", C.c_int64),
+                ("top", C.c_int32), ("left", C.c_int32), ("nh", C.c_int32), ("nw", C.c_int32)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("x", View), ("y", View), ("res", View),
                 ("kh", C.c_int32), ("kw", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
@@ -104,6 +111,8 @@ SIGNATURES = {
     "prpe_frame_ingest": (C.c_int, [_VP, _VP, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                     C.POINTER(C.c_float), _I, _P, _P]),
     "prpe_crop_resize_u8": (C.c_int, [_VP, _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P]),
+    "prpe_frame_ingest_multi": (C.c_int, [C.POINTER(IngestSrc), _I, _VP, _I, C.POINTER(C.c_float),
+                                          C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P]),
     "prpe_gallery_enrol": (C.c_int, [_P, _L, _I, _I, _P, _P, _I, _I, _P]),
     "prpe_gallery_topk_workspace_bytes": (C.c_int64, [_I, _I, _I]),
     "prpe_gallery_topk": (C.c_int, [_P, _L, _I, _I, _P, _I, _P, _I, _P, _P, _P, _F, _P, _P, _L, _P]),

@@ -411,13 +411,24 @@ class Engine:
         """``stem`` on uint8 source frames [B, Hs, Ws, 3] (any strides): prpe_frame_ingest resizes,
         pads and normalises them (``ingest``: a prpe.ingest.FrameIngest) straight into the same
         zero-bordered NHWC4 buffer, raising the same per-frame max|x| slots; no fp32 frames exist
-        in between. Everything after the fill is ``stem``'s."""
-        B0, Hs, Ws, _ = frames_u8.shape
+        in between. Everything after the fill is ``stem``'s. A sequence of frames [Hs_i, Ws_i, 3]
+        of different sizes, or an ``ingest`` with ``antialias=True``, goes through
+        prpe_frame_ingest_multi; a 4-D tensor without it takes the one launch of
+        prpe_frame_ingest, as before."""
+        multi = not isinstance(frames_u8, torch.Tensor) or ingest.antialias
+        frames = ops.frame_list(frames_u8) if multi else frames_u8
+        B0 = len(frames)
         H0, W0 = ingest.size
         buf = self._batch_buf("stem_buf", B0, (H0 + 6, W0 + 8, 4))
         amax = self.amax_slot(B0) if self.precision == 3 else None
-        ops.frame_ingest(frames_u8, buf[:, 3:3 + H0, 3:3 + W0, :], ingest.geometry(Hs, Ws), ingest.a, ingest.b,
-                         ingest.fill, ingest.swap_rb, y_amax=amax)
+        if multi:      # frames of different sizes, or the antialias filter: prpe_frame_ingest_multi (§5l)
+            ops.frame_ingest_multi(frames, buf[:, 3:3 + H0, 3:3 + W0, :],
+                                   [ingest.geometry(*f.shape[:2]) for f in frames], int(ingest.antialias),
+                                   ingest.a, ingest.b, ingest.fill, ingest.swap_rb, y_amax=amax)
+        else:
+            Hs, Ws = frames.shape[1:3]
+            ops.frame_ingest(frames, buf[:, 3:3 + H0, 3:3 + W0, :], ingest.geometry(Hs, Ws), ingest.a, ingest.b,
+                             ingest.fill, ingest.swap_rb, y_amax=amax)
         return self._stem_conv(buf, amax, H0, W0, pool)
 
     def _stem_conv(self, buf, amax, H0, W0, pool):

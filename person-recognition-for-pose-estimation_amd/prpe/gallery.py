@@ -135,8 +135,10 @@ class FaceIdentifier:
 
     @torch.no_grad()
     def embed_u8(self, frames_u8, ingest=None):
+        """``embed`` on uint8 source frames: a tensor [B, Hs, Ws, 3], or a sequence of frames
+        [Hs_i, Ws_i, 3] of different sizes (``CombinedModel.forward_u8``)."""
         m = self.model
-        frames_u8, ingest = m._check_input_u8(frames_u8, ingest)
+        frames_u8, ingest = m._check_input_u8(frames_u8, ingest, sequence=True)
         m._sync_weights()
         emb, _ = m.engine.adaface(m.engine.trunk_u8(frames_u8, ingest))
         return emb

@@ -160,14 +160,26 @@ class CombinedModel:
         """``forward`` on uint8 source frames [B, Hs, Ws, 3] on the device (any strides: an HWC
         batch, NCHW frames through ``permute(0, 2, 3, 1)``), at the source resolution. ``ingest``:
         a prpe.FrameIngest (default: letterbox to 640 x 640, raw / 255, RGB); prpe_frame_ingest
-        resizes and normalises them straight into the stem's buffer."""
-        frames_u8, ingest = self._check_input_u8(frames_u8, ingest)
+        resizes and normalises them straight into the stem's buffer. A sequence
+        of frames [Hs_i, Ws_i, 3] of different sizes is one batch too, and ``antialias=True`` in
+        the ingest filters every axis that shrinks (prpe_frame_ingest_multi)."""
+        frames_u8, ingest = self._check_input_u8(frames_u8, ingest, sequence=True)
         self._sync_weights()
         return self._task_head(self.engine.trunk_u8(frames_u8, ingest))
 
-    def _check_input_u8(self, x, ingest):
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4
-                and x.shape[3] == 3 and x.numel() > 0):
+    def _check_input_u8(self, x, ingest, sequence=False):
+        """``sequence``: the caller's whole-frame ingest also takes a sequence of uint8 frames
+        [Hs_i, Ws_i, 3] of different sizes; the crop stages do not."""
+        if isinstance(x, (list, tuple)):
+            if not sequence:
+                raise ValueError("a sequence of frames of different sizes is taken by the whole-frame ingest only "
+                                 "(forward_u8, forward_all_u8, FaceIdentifier): the crop stages resample from one "
+                                 "uint8 tensor [B,Hs,Ws,3]")
+            if not x or not all(isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == torch.uint8 and f.dim() == 3
+                                and f.shape[2] == 3 and f.numel() > 0 for f in x):
+                raise ValueError("expected a non-empty sequence of uint8 CUDA(HIP) frames [Hs,Ws,3]")
+        elif not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4
+                  and x.shape[3] == 3 and x.numel() > 0):
             raise ValueError("expected uint8 CUDA(HIP) frames [B,Hs,Ws,3]")
         if ingest is None:
             ingest = FrameIngest()
@@ -227,7 +239,7 @@ class CombinedModel:
     @torch.no_grad()
     def forward_all_u8(self, frames_u8, ingest=None, face_stride=None, concurrent=True):
         """``forward_all`` on uint8 source frames [B, Hs, Ws, 3] (see ``forward_u8``)."""
-        frames_u8, ingest = self._check_input_u8(frames_u8, ingest)
+        frames_u8, ingest = self._check_input_u8(frames_u8, ingest, sequence=True)
         self._sync_weights()
         return self._all_heads(self.engine.trunk_u8(frames_u8, ingest), face_stride, concurrent)
 

@@ -12,7 +12,7 @@ import math
 
 import torch
 
-from ._lib import ACT, RES_NONE, BneckDesc, ConvDesc, PrpeError, StemDesc, View, check, lib
+from ._lib import ACT, RES_NONE, BneckDesc, ConvDesc, IngestSrc, PrpeError, StemDesc, View, check, lib
 from .arch import VIT_IMG
 
 
@@ -688,6 +688,66 @@ def frame_ingest(frames, y, region, a, b, fill=(0.0, 0.0, 0.0), swap_rb=False, y
     check(lib().prpe_frame_ingest(C.byref(fv), C.byref(view(y)), top, left, nh, nw, _f3(what, "a", a),
                                   _f3(what, "b", b), _f3(what, "fill", fill), int(bool(swap_rb)), _ptr(y_amax),
                                   _stream()), what)
+    return y
+
+
+INGEST_MAX_SCALE = 32      # prpe_frame_ingest_multi, filter 1: the largest downscale per axis
+
+
+def frame_list(frames):
+    """The frames of a batch as a list: a 4-D tensor is taken as its frames, a sequence as it is."""
+    if isinstance(frames, torch.Tensor):
+        return list(frames.unbind(0)) if frames.dim() == 4 else [frames]
+    return list(frames)
+
+
+def frame_ingest_multi(frames, y, geoms, filter, a, b, fill=(0.0, 0.0, 0.0), swap_rb=False, y_amax=None):
+    """``frame_ingest`` for frames of different sizes, and with an antialiased downscale
+    (prpe_frame_ingest_multi, include/prpe.h). ``frames``: a sequence of B uint8 device tensors
+    [Hs_i, Ws_i, 3], any strides (a 4-D tensor is taken as its frames). ``geoms``: B regions (top,
+    left, nh, nw), a sequence or an int tensor [B, 4] (``FrameIngest.geometry_batch``). ``filter``:
+    0 bilinear (``frame_ingest``'s bytes, frame by frame), 1 antialias (torch's triangle filter on
+    every axis that shrinks, by at most 32). The table of frames is built here, on the host, and
+    travels in the kernel arguments. Every check made here raises ``ValueError``."""
+    what = "prpe_frame_ingest_multi"
+    frames = frame_list(frames)
+    B = len(frames)
+    if B < 1:
+        raise ValueError(f"{what}: no frames")
+    for n, f in enumerate(frames):
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8:
+            raise ValueError(f"{what}: frame {n} must be a uint8 tensor, got "
+                             f"{getattr(f, 'dtype', type(f).__name__)}")
+        if f.dim() != 3 or f.shape[2] != 3 or f.numel() == 0:
+            raise ValueError(f"{what}: frame {n} must be [Hs, Ws, 3] (3 channels last), got {list(f.shape)}")
+    if filter not in (0, 1):
+        raise ValueError(f"{what}: filter must be 0 (bilinear) or 1 (antialias), got {filter!r}")
+    geoms = geoms.tolist() if isinstance(geoms, torch.Tensor) else [tuple(g) for g in geoms]
+    if len(geoms) != B or any(len(g) != 4 for g in geoms):
+        raise ValueError(f"{what}: {B} frames need {B} regions (top, left, nh, nw), got {len(geoms)}")
+    if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 4):
+        raise ValueError(f"{what}: y must be a float32 device tensor [B, H, W, 4]")
+    if y.shape[0] != B or y.shape[3] != 4 or y.stride(3) != 1 or y.data_ptr() % 16 or \
+            any(s % 4 for s in y.stride()[:3]):
+        raise ValueError(f"{what}: y must be [{B}, H, W, 4] with 4 contiguous, 16-byte aligned channels, got "
+                         f"{list(y.shape)} strides {list(y.stride())}")
+    table = (IngestSrc * B)()
+    for n, (f, g) in enumerate(zip(frames, geoms)):
+        if not f.is_cuda or f.device != y.device:
+            raise ValueError(f"{what}: frame {n} must be on {y.device}, got one on {f.device}")
+        top, left, nh, nw = (int(v) for v in g)
+        if nh < 1 or nw < 1 or top < 0 or left < 0 or top + nh > y.shape[1] or left + nw > y.shape[2]:
+            raise ValueError(f"{what}: region {(top, left, nh, nw)} of frame {n} is empty or not inside "
+                             f"{list(y.shape[1:3])}")
+        Hs, Ws = f.shape[:2]
+        if filter and (Hs > INGEST_MAX_SCALE * nh or Ws > INGEST_MAX_SCALE * nw):
+            raise ValueError(f"{what}: frame {n}, {Hs} x {Ws} into {nh} x {nw}: the antialias filter shrinks an "
+                             f"axis by at most {INGEST_MAX_SCALE}")
+        table[n] = IngestSrc(f.data_ptr(), Hs, Ws, *f.stride(), top, left, nh, nw)
+    _check_slots(what, B, y_amax)
+    check(lib().prpe_frame_ingest_multi(table, B, C.byref(view(y)), int(filter), _f3(what, "a", a),
+                                        _f3(what, "b", b), _f3(what, "fill", fill), int(bool(swap_rb)),
+                                        _ptr(y_amax), _stream()), what)
     return y
 
 
