@@ -10,6 +10,9 @@
   every border row's two best core neighbours more than 2 tol apart (or exactly equal), with
   tol = 4 e_ref measured on the input as in tests/test_gpu_gallery.py. No row is left out on these
   grounds: the seeds and thresholds below were picked so that both hold, and it is asserted here;
+* the exact inputs of the multi-tile walk (tests/test_gpu_pairs_walk.py) with their conditions: the
+  ring of many tiles cut into arcs, ~200 clusters scattered over the tile rows, and the compaction
+  scan past one chunk with its per-group reference, pinned to ``dbscan_ref`` at a small chunk;
 * the ABI entries, every refusal of the header (the pointers below are never read), and the
   ``FaceClusters`` / ``FaceClustering`` bookkeeping with the ops calls stubbed.
 """
@@ -434,6 +437,241 @@ def test_chain_rows_are_a_ring_with_a_repeated_row():
     cut = np.ones(257, dtype=np.uint8)
     cut[[40, 130, 200]] = 0
     assert dbscan_ref(s, cut, 0.5, 1).n_clusters == 3
+
+
+# ---------------------------------------------------------------------------------- the tile walk
+# Inputs of tests/test_gpu_pairs_walk.py, at the sizes where every workgroup of the two pair passes
+# walks at least three 128 x 128 tiles (``walk_sizes``, tests/test_faceverif_host.py) and where
+# fc_compact_kernel scans more than one chunk of SCAN_CHUNK rows. Every input is exact: rows of
+# four +-0.5, whose fp32 scores x @ x.T are the fp64 ones, so every comparison is an equality.
+TILE = 128
+SCAN_CHUNK = 8192
+RING_CUTS = (40, 130, 200)
+RING_MIN_SAMPLES = (1, 40)
+
+
+def scores32(x):
+    """The fp32 score matrix of exact rows (multiples of 0.25, at most four terms a sum)."""
+    return x @ x.T
+
+
+def left_out_walk(n):
+    """Valid bytes with zeros on both sides of the first, a middle and the last tile border, at
+    rows 0 and 5 and at the last row (the padded tile row's only row when n = k T + 1)."""
+    valid = np.ones(n, dtype=np.uint8)
+    mid, last = (n // TILE // 2) * TILE, (n - 1) // TILE * TILE
+    valid[[0, 5, TILE - 1, TILE, mid - 1, mid, last - 1, last, n - 1]] = 0
+    return valid
+
+
+def ring_valid(n, cuts=RING_CUTS):
+    """``chain_rows(n, 512)`` repeats with period 256: row i scores 0.5 with the rows of residue
+    i +- 1 (mod 256) and 1.0 with those of its own. Leaving out every row of three residues cuts
+    the ring of residues into three arcs, each with rows in tiles all over the triangle."""
+    return (~np.isin(np.arange(n) % 256, cuts)).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def ring_case(n):
+    """(rows, valid, fp32 scores) of the cut ring of n rows; the arrays are shared: do not write them."""
+    x = chain_rows(n, 512)
+    return x, ring_valid(n), scores32(x)
+
+
+def same_partition(cluster_a, cluster_b):
+    """Two cluster id vectors over the same rows name the same partition (and the same rows -1)."""
+    pairs = {(int(a), int(b)) for a, b in zip(cluster_a, cluster_b)}
+    return (len(pairs) == len({a for a, _ in pairs}) == len({b for _, b in pairs})
+            and bool(((np.asarray(cluster_a) < 0) == (np.asarray(cluster_b) < 0)).all()))
+
+
+SCATTERED = dict(D=96, seed=4200, threshold=0.75, min_samples=6, satellites=160, loners=25)
+
+
+def scattered_rows(n, D, seed, satellites, loners):
+    """Many small clusters whose members lie all over the rows. The last 18 columns are a pool of
+    "extra" columns, the others 3-column triples; a group is a triple with one of 8 sign patterns
+    (two groups' triples score at most 0.25 with each other). A member holds its group's triple
+    and one seeded extra entry: two members of a group score 0.75, +-0.25 when they share the
+    extra column; members of different groups at most 0.5. A satellite holds two columns of a
+    group's triple and two extra entries: 0.75 with the few members that share one of those (also
+    of the sibling group that differs in the third sign only), below that with all others. A loner
+    holds four extra entries. A seeded permutation scatters all of them. Returns the rows and, per
+    row, the group (-1: satellite, -2: loner)."""
+    g = np.random.default_rng(seed)
+    base, pool = D - 18, 18
+    groups = base // 3 * 8
+    x = np.zeros((n, D), dtype=np.float32)
+    group = np.empty(n, dtype=np.int64)
+    members = n - satellites - loners
+    for k in range(n):
+        if k < members:
+            group[k] = k % groups
+            t, sg = divmod(k % groups, 8)
+            for e in range(3):
+                x[k, 3 * t + e] = -0.5 if sg >> e & 1 else 0.5
+            x[k, base + g.integers(pool)] = g.choice([-0.5, 0.5])
+        elif k < members + satellites:
+            group[k] = -1
+            t, sg = divmod(int(g.integers(groups)), 8)
+            for e in (0, 1):
+                x[k, 3 * t + e] = -0.5 if sg >> e & 1 else 0.5
+            x[k, base + g.choice(pool, 2, replace=False)] = g.choice([-0.5, 0.5], 2)
+        else:
+            group[k] = -2
+            x[k, base + g.choice(pool, 4, replace=False)] = g.choice([-0.5, 0.5], 4)
+    perm = g.permutation(n)
+    return x[perm], group[perm]
+
+
+@functools.lru_cache(maxsize=None)
+def scattered_case(n):
+    """(rows, group, valid, fp32 scores, dbscan_ref) of the scattered clusters at n rows; shared."""
+    x, group = scattered_rows(n, SCATTERED["D"], SCATTERED["seed"], SCATTERED["satellites"], SCATTERED["loners"])
+    valid = left_out_walk(n)
+    s = scores32(x)
+    return x, group, valid, s, dbscan_ref(s, valid, SCATTERED["threshold"], SCATTERED["min_samples"])
+
+
+def _patterns(count, seed):
+    """``count`` distinct rows of four +-0.5 in 32 columns: any two score at most 0.75."""
+    import itertools
+    combos = np.array(list(itertools.combinations(range(32), 4)))
+    assert count <= 16 * len(combos)
+    order = np.random.default_rng(seed).permutation(16 * len(combos))[:count]
+    x = np.zeros((count, 32), dtype=np.float32)
+    for k, o in enumerate(order):
+        for e in range(4):
+            x[k, combos[o // 16, e]] = -0.5 if o % 16 >> e & 1 else 0.5
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def scan_case(n, chunk=SCAN_CHUNK, seed=4300):
+    """Input and expected result of the compaction scan past one chunk, at threshold 1.0 and
+    min_samples 2 on D = 32 rows: two rows are neighbours exactly when they are the same pattern,
+    so the score matrix is block-sparse by construction and the reference is written per group
+    (no n x n matrix): a pattern's rows that take part are one cluster rooted at the lowest when
+    there are two or more, noise when there is one. Walking the rows upwards, a free row becomes a
+    cluster root with 1 to 3 further members at seeded free rows up to chunk / 8 above, a noise
+    row with a pattern of its own, or a left-out row (valid 0) that repeats an earlier row's
+    pattern. Rows chunk - 1, chunk, 2 chunk - 1 and 2 chunk are roots. Returns (rows, valid, Ref)."""
+    assert n > 2 * chunk + 2
+    g = np.random.default_rng(seed)
+    pat = np.full(n, -1, dtype=np.int64)
+    valid = np.ones(n, dtype=np.uint8)
+    reserved = np.zeros(n, dtype=bool)
+    forced = [chunk - 1, chunk, 2 * chunk - 1, 2 * chunk]
+    reserved[forced] = True
+    npat = 0
+    for i in range(n):
+        if pat[i] >= 0:
+            continue
+        u = g.random()
+        free = i + 1 + np.flatnonzero((pat[i + 1:i + 1 + chunk // 8] < 0) & ~reserved[i + 1:i + 1 + chunk // 8])
+        if (reserved[i] or u < 0.45) and free.size:
+            pat[i] = npat
+            pat[g.choice(free, min(int(g.integers(1, 4)), free.size), replace=False)] = npat
+            npat += 1
+        elif u < 0.8 or i == 0:
+            pat[i] = npat
+            npat += 1
+        else:
+            pat[i] = pat[g.integers(i)]
+            valid[i] = 0
+    x = _patterns(npat, seed + 1)[pat]
+    root = np.full(n, -1, dtype=np.int64)
+    kind = np.where(valid != 0, NOISE, LEFT_OUT).astype(np.int64)
+    degree = np.zeros(n, dtype=np.int64)
+    rows_of = collections.defaultdict(list)
+    for i in np.flatnonzero(valid):
+        rows_of[int(pat[i])].append(int(i))
+    for rows in rows_of.values():
+        degree[rows] = len(rows) - 1
+        if len(rows) >= 2:
+            root[rows], kind[rows] = rows[0], CORE
+    roots = np.unique(root[root >= 0])
+    cluster = np.where(root >= 0, np.searchsorted(roots, root), -1)
+    assert all(root[r] == r for r in forced)
+    return x, valid, Ref(root, kind, degree, cluster, np.bincount(cluster[cluster >= 0]).astype(np.int64), len(roots))
+
+
+def test_ring_of_many_tiles_meets_its_conditions():
+    """At the 4865 rows of a 256-CU device: three clusters, each with rows in at least 19 of the
+    39 tile rows (an arc inside one half of the residues lies in every second tile row), each
+    rooted at its lowest (core) row. At min_samples 40 the rows next to a cut are border rows
+    (degree 37: 18 of their own residue, 19 on one side) whose core neighbours all score 0.5, so
+    the lowest row decides; everything else that takes part is core (degree >= 56)."""
+    tn, n = 39, 4865
+    x, valid, s = ring_case(n)
+    assert np.array_equal(s[:300], (x[:300].astype(np.float64) @ x.astype(np.float64).T).astype(np.float32))
+    res = np.arange(n) % 256
+    for ms in RING_MIN_SAMPLES:
+        ref = dbscan_ref(s, valid, 0.5, ms)
+        assert ref.n_clusters == 3 and (ref.kind[valid == 0] == LEFT_OUT).all() and (ref.kind != NOISE).all()
+        for c in range(3):
+            rows = np.flatnonzero(ref.cluster == c)
+            assert np.unique(rows // TILE).size >= (tn - 1) // 2
+            assert (ref.root[rows] == rows[ref.kind[rows] == CORE].min()).all()
+        next_to_cut = np.isin(res, [r + d for r in RING_CUTS for d in (-1, 1)])
+        if ms == 1:
+            assert (ref.kind[valid != 0] == CORE).all()
+            continue
+        assert (ref.kind[next_to_cut] == BORDER).all() and (ref.kind[(valid != 0) & ~next_to_cut] == CORE).all()
+        assert ref.degree[next_to_cut].max() == 37 and ref.degree[(valid != 0) & ~next_to_cut].min() == 56
+        for i in np.flatnonzero(next_to_cut)[::7]:
+            cand = s[i, (ref.kind == CORE) & (s[i] >= 0.5) & (valid != 0)]
+            assert cand.size >= 19 and (cand == 0.5).all()
+
+
+def test_scattered_clusters_meet_their_conditions():
+    tn, n = 39, 4865
+    x, group, valid, s, ref = scattered_case(n)
+    thr = np.float32(SCATTERED["threshold"])
+    assert np.array_equal(s[:300], (x[:300].astype(np.float64) @ x.astype(np.float64).T).astype(np.float32))
+    assert ((x * x).sum(axis=1) == 1).all()
+    counts = np.bincount(ref.kind, minlength=4)
+    assert ref.n_clusters >= 50 and counts[NOISE] > 0 and counts[BORDER] > 0 and counts[CORE] > 0
+    assert counts[LEFT_OUT] == 8 and np.array_equal(np.flatnonzero(valid == 0),
+                                                    [0, 5, 127, 128, 19 * 128 - 1, 19 * 128, n - 2, n - 1])
+    spread = [np.unique(np.flatnonzero(ref.cluster == c) // TILE).size for c in range(ref.n_clusters)]
+    assert np.median(spread) >= 3 and min(spread) >= 3
+    on = valid != 0
+    pair = on[:, None] & on[None, :] & ~np.eye(n, dtype=bool)
+    assert (s[pair] == thr).any() and (s[pair] > thr).any() and (s[pair] < thr).any()
+    # a border row between two clusters whose best core neighbours tie: the lowest row decides
+    decided = 0
+    for i in np.flatnonzero(ref.kind == BORDER):
+        cand = np.flatnonzero(pair[i] & (s[i] >= thr) & (ref.kind == CORE))
+        best = cand[s[i, cand] == s[i, cand].max()]
+        decided += np.unique(ref.cluster[best]).size > 1
+    print(f"scattered n={n}: clusters={ref.n_clusters} kinds={counts.tolist()} median tile rows={np.median(spread)} "
+          f"border rows tied between clusters={decided}")
+    assert decided >= 1
+
+
+def test_scan_case_is_dbscan_ref_at_a_small_chunk_and_meets_its_conditions():
+    """The per-group reference of ``scan_case`` against ``dbscan_ref`` with the chunk scaled down
+    to 64 rows; at the real chunk: core roots, noise and left-out rows in every scan pass, roots
+    on both sides of both chunk borders, ids ascending with the root."""
+    for seed in (1, 2, 3):
+        x, valid, ref = scan_case(2 * 64 + 50, chunk=64, seed=seed)
+        assert same_ref(ref, dbscan_ref(scores32(x), valid, 1.0, 2))
+        assert all(ref.root[r] == r for r in (63, 64, 127, 128))
+    n = 2 * SCAN_CHUNK + 3 * TILE + 1
+    x, valid, ref = scan_case(n)
+    assert n == 131 * TILE + 1 and ((x * x).sum(axis=1) == 1).all()
+    is_root = ref.root == np.arange(n)
+    assert is_root[[SCAN_CHUNK - 1, SCAN_CHUNK, 2 * SCAN_CHUNK - 1, 2 * SCAN_CHUNK]].all()
+    for p in range(3):
+        rows = slice(p * SCAN_CHUNK, min((p + 1) * SCAN_CHUNK, n))
+        assert is_root[rows].sum() >= 20 and {LEFT_OUT, NOISE, CORE} == set(ref.kind[rows].tolist())
+    assert np.array_equal(ref.cluster[is_root], np.arange(ref.n_clusters)) and ref.n_clusters > 1000
+    assert (ref.kind[valid == 0] == LEFT_OUT).all() and ref.sizes.sum() == (ref.kind == CORE).sum()
+    # a cluster has members in a later pass than its root, and a left-out row repeats a live pattern
+    assert (ref.root[2 * SCAN_CHUNK:] < 2 * SCAN_CHUNK)[ref.root[2 * SCAN_CHUNK:] >= 0].any()
+    some = np.flatnonzero(valid == 0)[:200]
+    assert any((x[valid != 0] == x[i]).all(axis=1).any() for i in some)
 
 
 # ---------------------------------------------------------------------------------- ABI and refusals

@@ -5,6 +5,8 @@
   each pinned here to a second, plain statement in Python loops;
 * the bin rule at its edges, which pairs count, hand-worked curves, and the equivalence the design
   rests on: FA[b] == #(score >= fp32 edge_b);
+* the sizes, inputs and blocked reference of the multi-tile walk (tests/test_gpu_pairs_walk.py):
+  three tiles per workgroup from the CU count, exact rows, labels of both classes in every tile;
 * the ABI entry, every refusal of the header (the pointers below are never read), and
   ``FaceVerification`` / ``FaceIdentifier.calibrate`` bookkeeping with the ops call stubbed.
 """
@@ -305,6 +307,150 @@ def test_false_accepts_at_an_edge_are_the_scores_at_or_above_it(nbins):
     for b in range(nbins + 1):
         assert FA[b] == int((s >= np.float32(thr[b])).sum()), b
     _check_curve_against_loops(hist, (1e-1, 1e-2, 1e-3, 1e-4))
+
+
+# ---------------------------------------------------------------------------------- the tile walk
+# Sizes and inputs of tests/test_gpu_pairs_walk.py: prpe_pair_hist's grid is min(tiles, CUs) workgroups,
+# each walking the 128 x 128 score tiles id, id + grid, ..; these are the sizes at which every
+# workgroup walks at least three.
+TILE = 128
+
+
+def walk_sizes(cus):
+    """(tile rows tn, rows n) of the self-mode walk on a device of ``cus`` compute units: the
+    smallest tn whose triangle tn (tn + 1) / 2 holds 3 tiles per workgroup, and n = (tn - 1) T + 1,
+    so that the last tile row holds one row and is padded."""
+    tn = 1
+    while tn * (tn + 1) // 2 < 3 * cus:
+        tn += 1
+    return tn, (tn - 1) * TILE + 1
+
+
+def walk_sizes_cross(cus):
+    """(tm, tn, M, N) of the cross-mode walk: tm about sqrt(3 cus / 2.75) (17 at 256 CUs), tn the
+    smallest with tm tn >= 3 cus and tn != tm; M and N one row past a tile multiple."""
+    tm = max(2, math.ceil(math.sqrt(3 * cus / 2.75)))
+    tn = -(-3 * cus // tm)
+    if tn == tm:
+        tn += 1
+    return tm, tn, (tm - 1) * TILE + 1, (tn - 1) * TILE + 1
+
+
+def tiles_of(m, n=None):
+    """Score tiles prpe_pair_hist walks: the upper triangle of m rows, or the m x n rectangle."""
+    tm = -(-m // TILE)
+    return tm * (tm + 1) // 2 if n is None else tm * -(-n // TILE)
+
+
+def four_halves(n, D, seed, pool=24):
+    """Rows with four entries of +-0.5 among ``pool`` seeded columns: the norm is exactly 1 and
+    every dot product a multiple of 0.25, equal in any arithmetic (float32 included)."""
+    g = np.random.default_rng(seed)
+    cols = np.sort(g.permutation(D)[:pool])
+    x = np.zeros((n, D), dtype=np.float32)
+    for i in range(n):
+        x[i, g.choice(cols, 4, replace=False)] = g.choice([-0.5, 0.5], 4)
+    return x
+
+
+def walk_labels(n, seed, classes=4):
+    """(labels, valid) for n rows: a seeded label of ``classes`` per row, so that genuine and
+    impostor pairs meet in every tile; label -1 at a few seeded rows and at one tile border; valid
+    bytes 0 on both sides of the first, a middle and the last tile border, at row 5 and at the
+    last row (which is the padded tile row's only row when n = k T + 1)."""
+    g = np.random.default_rng(seed)
+    labels = g.integers(0, classes, n).astype(np.int64)
+    labels[g.choice(n, min(7, n), replace=False)] = -1
+    valid = np.ones(n, dtype=np.uint8)
+    if n > 2 * TILE:
+        labels[2 * TILE - 1] = -1
+        last = (n - 1) // TILE * TILE
+        mid = (n // TILE // 2) * TILE
+        valid[[TILE - 1, TILE, mid - 1, mid, last - 1, last]] = 0
+    valid[[min(5, n - 1), n - 1]] = 0
+    return labels, valid
+
+
+def pair_hist_ref_blocks(a, b, la, lb, va, vb, nbins, block=1024):
+    """``pair_hist_ref`` for several ``nbins`` at once without the whole score matrix: fp32 scores
+    a[r0:r1] @ b.T of ``block`` rows at a time (exact for ``four_halves`` rows; a row with a NaN
+    makes every score of it NaN, as on the device), b None for self mode (pairs i < j).
+    Returns {nbins: hist}, skipped."""
+    self_mode = b is None
+    if self_mode:
+        b, lb, vb = a, la, va
+    la, lb = np.asarray(la, dtype=np.int64), np.asarray(lb, dtype=np.int64)
+    ra = la >= 0 if va is None else (la >= 0) & (np.asarray(va) != 0)
+    rb = lb >= 0 if vb is None else (lb >= 0) & (np.asarray(vb) != 0)
+    hists = {nb: np.zeros((2, nb), dtype=np.int64) for nb in nbins}
+    skipped = 0
+    cols = np.arange(b.shape[0])
+    for r0 in range(0, a.shape[0], block):
+        r1 = min(r0 + block, a.shape[0])
+        with np.errstate(invalid="ignore"):
+            s = a[r0:r1] @ b.T
+        on = ra[r0:r1, None] & rb[None, :]
+        if self_mode:
+            on &= np.arange(r0, r1)[:, None] < cols[None, :]
+        fin = np.isfinite(s)
+        skipped += int((on & ~fin).sum())
+        on &= fin
+        same = la[r0:r1, None] == lb[None, :]
+        gen, imp = s[on & same], s[on & ~same]
+        for nb in nbins:
+            hists[nb][0] += np.bincount(bin_ref(gen, nb), minlength=nb)
+            hists[nb][1] += np.bincount(bin_ref(imp, nb), minlength=nb)
+    return hists, skipped
+
+
+def test_walk_sizes_give_three_tiles_per_workgroup():
+    assert walk_sizes(256) == (39, 4865) and tiles_of(4865) == 780
+    assert walk_sizes_cross(256) == (17, 46, 2049, 5761) and tiles_of(2049, 5761) == 782
+    for cus in (1, 8, 64, 80, 104, 120, 228, 256, 304):
+        tn, n = walk_sizes(cus)
+        assert tiles_of(n) >= 3 * cus > (tn - 1) * tn // 2 and n % TILE == 1 and -(-n // TILE) == tn
+        tm, tc, M, N = walk_sizes_cross(cus)
+        assert tiles_of(M, N) == tm * tc >= 3 * cus and M != N and M % TILE == 1 and N % TILE == 1
+
+
+def test_walk_inputs_are_exact_and_both_classes_meet_in_every_full_tile():
+    """The multi-tile inputs: fp32 scores of ``four_halves`` rows equal the fp64 ones; with
+    ``walk_labels`` every tile of full tile rows holds genuine and impostor pairs that count, the
+    padded tile row holds none (its one row is left out), and both borders of three tiles are
+    left out."""
+    tn, n = walk_sizes(256)
+    x = four_halves(n, 32, 4100)
+    s = x[:700] @ x.T
+    assert np.array_equal(s, (x[:700].astype(np.float64) @ x.astype(np.float64).T).astype(np.float32))
+    assert np.array_equal(np.unique(s * 4), np.arange(-4, 5))
+    assert ((x * x).sum(axis=1) == 1).all()
+    labels, valid = walk_labels(n, 4101)
+    on = (labels >= 0) & (valid != 0)
+    assert valid[n - 1] == 0 and not valid[[127, 128, 19 * 128 - 1, 19 * 128, n - 2]].any() and (labels < 0).sum() >= 8
+    for t in range(tn - 1):
+        tile = labels[t * TILE:(t + 1) * TILE][on[t * TILE:(t + 1) * TILE]]
+        assert set(tile.tolist()) == {0, 1, 2, 3} and (np.bincount(tile) >= 2).all()
+    assert not on[(tn - 1) * TILE:].any()
+
+
+def test_blocked_reference_is_pair_hist_ref():
+    g = np.random.default_rng(77)
+    n, m = 301, 140
+    x = four_halves(n + m, 32, 78)
+    x[[3, 130, n - 1], 0] = np.nan
+    x[n + 7, 5] = np.inf
+    la, va = walk_labels(n, 79)
+    lb, vb = g.integers(-1, 3, m), (g.random(m) > 0.1).astype(np.uint8)
+    with np.errstate(invalid="ignore"):
+        s_self, s_cross = x[:n] @ x[:n].T, x[:n] @ x[n:].T
+    for valid in (None, va):
+        got, skipped = pair_hist_ref_blocks(x[:n], None, la, None, valid, None, (256, 4096), block=64)
+        for nbins in (256, 4096):
+            want, want_skipped = pair_hist_ref(s_self, la, la, valid, valid, nbins, True)
+            assert np.array_equal(got[nbins], want) and skipped == want_skipped > 0
+    got, skipped = pair_hist_ref_blocks(x[:n], x[n:], la, lb, va, vb, (512,), block=100)
+    want, want_skipped = pair_hist_ref(s_cross, la, lb, va, vb, 512, False)
+    assert np.array_equal(got[512], want) and skipped == want_skipped > 0
 
 
 # ---------------------------------------------------------------------------------- ABI and refusals

@@ -6,7 +6,9 @@ above them -- against the host restatements of tests/test_clusters_host.py (``db
 Every output and the workspace live in sentinel-filled buffers with guards on both sides
 (``Guarded``, tests/test_gpu_rowops.py); every run is followed by a check that the guards are
 untouched. T = ops.PAIR_HIST_TILE: the shapes sit on both sides of one and two tiles, and 2 T + 1
-rows give six triangle tiles, so unions have to cross tiles.
+rows give six triangle tiles, so unions have to cross tiles. Six tiles are fewer than the CUs, so
+every workgroup here takes one tile: the walk of several tiles per workgroup (4865 rows on 256 CUs)
+and the compaction scan past one 8192-row chunk are tested in tests/test_gpu_pairs_walk.py.
 
 * exact inputs (rows of four +-0.5) must give ``dbscan_ref`` / ``sums_ref`` exactly at thresholds
   that sit on attainable scores; chains (a ring of 0.5 links through every tile) and their

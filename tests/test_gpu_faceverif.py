@@ -4,7 +4,9 @@ host restatements of tests/test_faceverif_host.py (``pair_hist_ref``, ``curve_re
 
 ``hist`` and ``skipped`` live in sentinel-filled buffers with guards on both sides (``Guarded``,
 tests/test_gpu_rowops.py); every launch is followed by a check that the guards are untouched.
-T = ops.PAIR_HIST_TILE: the shapes sit on both sides of one and two tiles.
+T = ops.PAIR_HIST_TILE: the shapes sit on both sides of one and two tiles. At most nine tiles are
+fewer than the CUs, so every workgroup here takes one tile: the walk of several tiles per workgroup
+(4865 rows, cross 2049 x 5761, on 256 CUs) is tested in tests/test_gpu_pairs_walk.py.
 
 * exact inputs (rows of four +-0.5: unit norm, every dot product a multiple of 0.25, exact in any
   order) must give the integer counts of fp64, in self and cross mode, at every nbins;
