@@ -1050,6 +1050,81 @@ int prpe_cluster_centroids(const float* a, int64_t a_row_stride, int32_t N, int3
                            const int32_t* n_clusters, int32_t max_clusters, int64_t* sums, float* centroids,
                            void* stream);
 
+/*
+ * NV12 frames in (csrc/nv12.hip; additive to ABI 12): what a hardware video decoder
+ * hands over -- a full-resolution luma plane, a half-resolution plane of interleaved chroma pairs
+ * and a row pitch wider than the picture -- read by the stem and crop stages themselves, with no
+ * conversion pass and no RGB copy in front of them. The reference reads decoded images only; the
+ * semantics are this project's.
+ *
+ * The source. Odd h and w are legal: the chroma plane has the rounded-up size. y and uv may be two
+ * allocations, or two views of one decoder surface (the chroma rows following the aligned luma
+ * rows at the same pitch). Bytes between w and the pitch, and rows below h, are never read.
+ */
+typedef struct prpe_nv12 {
+  const uint8_t* y;     /* device, logical [n, h, w], element stride 1 along w */
+  const uint8_t* uv;    /* device, logical [n, (h+1)/2, (w+1)/2, 2] = (U, V), 2 contiguous bytes per pair */
+  int32_t n, h, w;
+  int64_t y_sn, y_sh;   /* bytes; y_sh >= w (the decoder's pitch) */
+  int64_t uv_sn, uv_sh; /* bytes; uv_sh >= 2 * ((w+1)/2) */
+} prpe_nv12;
+
+/*
+ * The conversion: one rule, in integers, so that a host restatement is exact.
+ *   Chroma is replicated: pixel (i, j) takes the pair at (i >> 1, j >> 1) (nearest siting).
+ *   coef = (y_off, cy, crv, cgu, cgv, cbu): a HOST array of 6 int32; it travels in the kernel
+ *   arguments, as a, b and fill do.
+ *     C = Y - y_off;  D = U - 128;  E = V - 128
+ *     R = clamp(floor((cy*C + crv*E + 128) / 256), 0, 255)
+ *     G = clamp(floor((cy*C - cgu*D - cgv*E + 128) / 256), 0, 255)
+ *     B = clamp(floor((cy*C + cbu*D + 128) / 256), 0, 255)
+ *   floor on a negative numerator is an arithmetic shift right by 8. y_off must be in [0, 255] and
+ *   every other entry in [0, 4096]; the sums then stay far inside 32 bits (below 2^22).
+ *   The named tables are round(256 x) of the real matrices (prpe/nv12.py):
+ *     bt601 limited (16, 298, 409, 100, 208, 516)     bt601 full (0, 256, 359, 88, 183, 454)
+ *     bt709 limited (16, 298, 459,  55, 136, 541)     bt709 full (0, 256, 403, 48, 120, 475)
+ *   with crv = 2(1 - Kr), cbu = 2(1 - Kb), cgu = cbu Kb / Kg, cgv = crv Kr / Kg, Kg = 1 - Kr - Kb;
+ *   limited range scales luma by 255/219 and chroma by 255/224.
+ *
+ * The one property everything is held to: a converted tap is a uint8 value, so each fused entry
+ * point below has, bit for bit, the output of its _u8 twin run on the frames prpe_nv12_to_rgb
+ * writes -- the same coordinates, weights, lerps, affine, fill, clamp and y_amax. No new floating-
+ * point rule exists; the new arithmetic is the integer conversion alone. The fused entry points
+ * have no swap_rb: output channels 0, 1, 2 are R, G, B, which is what the u8 route gives on a
+ * conversion made in the ingest's own channel order. A tap outside the frame in a crop stage is raw
+ * 0 in all three channels (as in the _u8 kernels), not the conversion of a zero triple.
+ *
+ * All five are stream-ordered, allocate nothing and decide every refusal before the launch.
+ *
+ * nv12_to_rgb: out, packed uint8 [n, h, w, 3] with row stride osh and frame stride osn in bytes
+ *   (osh >= 3 w); swap_rb != 0 writes B, G, R. The unfused route and the yardstick of the others.
+ *   8-byte loads and stores are used where the planes, out and all their strides are 8-byte
+ *   aligned; any alignment is legal. Padding bytes of out are never written.
+ * frame_ingest_nv12: prpe_frame_ingest (y, region, a, b, fill, y_amax as there) on converted taps.
+ * crop_resize_nv12, roi_resize_nv12, roi_warp_nv12: prpe_crop_resize_u8, prpe_roi_resize_u8 and
+ *   prpe_roi_warp_u8 on converted taps; crop_meta's windows are in the pixels of these frames.
+ * -EINVAL, nothing launched: every refusal of the respective twin; a null src, coef or plane; n
+ *   below 1; a side below 1 or above 2^24; a pitch below the row (y_sh < w,
+ *   uv_sh < 2 * ((w+1)/2), osh < 3 w); an odd uv pointer, uv_sn or uv_sh (a pair is one aligned
+ *   16-bit load); a coefficient out of range; n != y->n for the ingest; a null out. No argument
+ *   makes a kernel read outside [0, h) x [0, w) of the luma plane or outside the rounded-up chroma
+ *   plane: indices are clamped or bounds-tested before they are used, as in the twins.
+ */
+int prpe_nv12_to_rgb(const prpe_nv12* src, const int32_t* coef /* HOST: 6 */, int32_t swap_rb, uint8_t* out,
+                     int64_t osn, int64_t osh, void* stream);
+int prpe_frame_ingest_nv12(const prpe_nv12* src, const int32_t* coef /* HOST: 6 */, const prpe_view* y, int32_t top,
+                           int32_t left, int32_t nh, int32_t nw, const float* a, const float* b, const float* fill,
+                           float* y_amax /* optional */, void* stream);
+int prpe_crop_resize_nv12(const prpe_nv12* src, const int32_t* coef /* HOST: 6 */, const float* crop_meta,
+                          const int32_t* n_crops, int32_t max_crops, const float* a, const float* b, float* crops,
+                          void* stream);
+int prpe_roi_resize_nv12(const prpe_nv12* src, const int32_t* coef /* HOST: 6 */, const float* crop_meta,
+                         const int32_t* n_crops, int32_t max_crops, const prpe_view* y, const float* a,
+                         const float* b, float* y_amax /* optional */, void* stream);
+int prpe_roi_warp_nv12(const prpe_nv12* src, const int32_t* coef /* HOST: 6 */, const float* crop_meta,
+                       const int32_t* n_crops, int32_t max_crops, const float* warp, const prpe_view* y,
+                       const float* a, const float* b, float* y_amax /* optional */, void* stream);
+
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse
  * a library built from other sources than the ones beside it. */

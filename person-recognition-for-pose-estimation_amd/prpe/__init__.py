@@ -14,13 +14,14 @@ from .faces import FaceCrops, PersonRecognition  # noqa: F401
 from .gallery import FaceGallery, FaceIdentifier  # noqa: F401
 from .ingest import FrameIngest  # noqa: F401
 from .model import CombinedModel, PoseOutput  # noqa: F401
+from .nv12 import NV12Frames  # noqa: F401
 from .postproc import keypoints_from_heatmaps, non_max_suppression, non_max_suppression_padded  # noqa: F401
 from .topdown import TopDownPose  # noqa: F401
 from .tracks import PersonTracker  # noqa: F401
 from .verification import FaceVerification  # noqa: F401
 
 __all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "CocoKeypointGT", "coco_keypoint_eval",
-           "TopDownPose", "FrameIngest", "FaceGallery", "FaceIdentifier", "FaceVerification",
+           "TopDownPose", "FrameIngest", "NV12Frames", "FaceGallery", "FaceIdentifier", "FaceVerification",
            "FaceClusters", "FaceClustering", "FaceCrops", "PersonRecognition", "PersonTracker",
            "non_max_suppression",
            "non_max_suppression_padded", "keypoints_from_heatmaps", "state_dict_spec", "TASKS"]

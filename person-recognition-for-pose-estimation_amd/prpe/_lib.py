@@ -35,6 +35,13 @@ class IngestSrc(C.Structure):
                 ("top", C.c_int32), ("left", C.c_int32), ("nh", C.c_int32), ("nw", C.c_int32)]
 
 
+class NV12(C.Structure):
+    """prpe_nv12: the luma plane and the interleaved chroma plane of a batch of NV12 frames, strides in bytes."""
+    _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p),
+                ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("y_sn", C.c_int64), ("y_sh", C.c_int64), ("uv_sn", C.c_int64), ("uv_sh", C.c_int64)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("x", View), ("y", View), ("res", View),
                 ("kh", C.c_int32), ("kw", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
@@ -74,6 +81,8 @@ _I = C.c_int32
 _L = C.c_int64
 _F = C.c_float
 _VP = C.POINTER(View)
+_NP = C.POINTER(NV12)
+_C6 = C.POINTER(C.c_int32)           # the 6 conversion coefficients of the NV12 entry points (host)
 SIGNATURES = {
     "prpe_conv2d_workspace_bytes": (C.c_int64, [C.POINTER(ConvDesc)]),
     "prpe_conv2d": (C.c_int, [C.POINTER(ConvDesc), _P]),
@@ -131,6 +140,13 @@ SIGNATURES = {
     "prpe_face_align_fit": (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P]),
     "prpe_roi_warp": (C.c_int, [_VP, _P, _P, _I, _P, _VP, _P, _P]),
     "prpe_roi_warp_u8": (C.c_int, [_VP, _P, _P, _I, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _VP, _P, _P]),
+    "prpe_nv12_to_rgb": (C.c_int, [_NP, _C6, _I, _P, _L, _L, _P]),
+    "prpe_frame_ingest_nv12": (C.c_int, [_NP, _C6, _VP, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float), _P, _P]),
+    "prpe_crop_resize_nv12": (C.c_int, [_NP, _C6, _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
+    "prpe_roi_resize_nv12": (C.c_int, [_NP, _C6, _P, _P, _I, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
+    "prpe_roi_warp_nv12": (C.c_int, [_NP, _C6, _P, _P, _I, _P, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float), _P,
+                                     _P]),
     "prpe_track_update": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _F, _I, C.POINTER(C.c_float), _F, _I,
                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "prpe_coco_kp_match_workspace_bytes": (C.c_int64, [_I]),

@@ -23,6 +23,7 @@ import torch
 
 from . import arch, ops
 from ._lib import RES_POST, RES_PRE
+from .nv12 import NV12Frames
 from .pack import ConvPack, bn_affine, pack_conv, pack_matrix, pack_upconv_taps
 
 YOLO_BN_EPS = 1e-3
@@ -415,6 +416,8 @@ class Engine:
         of different sizes, or an ``ingest`` with ``antialias=True``, goes through
         prpe_frame_ingest_multi; a 4-D tensor without it takes the one launch of
         prpe_frame_ingest, as before."""
+        if isinstance(frames_u8, NV12Frames):
+            return self._stem_nv12(frames_u8, ingest, pool)
         multi = not isinstance(frames_u8, torch.Tensor) or ingest.antialias
         frames = ops.frame_list(frames_u8) if multi else frames_u8
         B0 = len(frames)
@@ -429,6 +432,33 @@ class Engine:
             Hs, Ws = frames.shape[1:3]
             ops.frame_ingest(frames, buf[:, 3:3 + H0, 3:3 + W0, :], ingest.geometry(Hs, Ws), ingest.a, ingest.b,
                              ingest.fill, ingest.swap_rb, y_amax=amax)
+        return self._stem_conv(buf, amax, H0, W0, pool)
+
+    def _stem_nv12(self, nv12, ingest, pool):
+        """``stem_u8`` on a prpe.NV12Frames: prpe_frame_ingest_nv12 converts every
+        tap as it gathers it; the output is RGB whatever ``ingest.channel_order`` says of uint8
+        sources. With ``ingest.antialias`` the frames are converted first, in the ingest's channel
+        order, into a staging buffer this engine owns (one batch size at a time, as the stem
+        buffer), and prpe_frame_ingest_multi filters that: the filter's semantics with no new
+        filter kernel."""
+        B0, Hs, Ws = nv12.shape
+        H0, W0 = ingest.size
+        buf = self._batch_buf("stem_buf", B0, (H0 + 6, W0 + 8, 4))
+        amax = self.amax_slot(B0) if self.precision == 3 else None
+        interior = buf[:, 3:3 + H0, 3:3 + W0, :]
+        if ingest.antialias:
+            key = ("nv12_rgb", B0, Hs, Ws)
+            rgb = self._aux.get(key)
+            if rgb is None:
+                for k in [k for k in self._aux if isinstance(k, tuple) and k[0] == "nv12_rgb"]:
+                    del self._aux[k]
+                rgb = self._aux[key] = torch.empty(B0, Hs, Ws, 3, device=self.device, dtype=torch.uint8)
+            nv12.to_rgb(ingest.channel_order, out=rgb)
+            ops.frame_ingest_multi(rgb, interior, [ingest.geometry(Hs, Ws)] * B0, 1, ingest.a, ingest.b, ingest.fill,
+                                   ingest.swap_rb, y_amax=amax)
+        else:
+            ops.frame_ingest_nv12(nv12, interior, ingest.geometry(Hs, Ws), ingest.a, ingest.b, ingest.fill,
+                                  y_amax=amax)
         return self._stem_conv(buf, amax, H0, W0, pool)
 
     def _stem_conv(self, buf, amax, H0, W0, pool):

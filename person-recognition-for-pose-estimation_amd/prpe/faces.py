@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import torch
 
-from . import arch, ops
+from . import arch, nv12, ops
 from .gallery import FaceGallery
 from .postproc import non_max_suppression_padded
 from .topdown import TopDownPose
@@ -118,11 +118,10 @@ class FaceCrops:
         m = self.model
         frames_u8, ingest = m._check_input_u8(frames_u8, ingest)
         m._sync_weights()
-        B, Hs, Ws, _ = frames_u8.shape
+        B, Hs, Ws = frames_u8.shape[:3]
         return self._crops_to_identities(
             B, (Hs, Ws), dets, counts, (1.0, 1.0),
-            lambda meta, n_crops, y, amax: ops.roi_resize_u8(frames_u8, meta, n_crops, y, ingest.a, ingest.b,
-                                                             ingest.swap_rb, y_amax=amax))
+            lambda meta, n_crops, y, amax: nv12.roi_resize_src(frames_u8, meta, n_crops, y, ingest, y_amax=amax))
 
     # ------------------------------------------------------------------ the stage
     def _crops_to_identities(self, B, frame_hw, dets, counts, scale, resize, max_per_frame=None, identify=True,
@@ -222,11 +221,10 @@ class FaceCrops:
         det = e.yolo("yolo_face", e.trunk_u8(frames_u8, ingest), m._stride(m.yolo_face))
         dets, counts = non_max_suppression_padded(det)
         dets = _to_source(dets, _scale_xy(self.box_scale, ingest.size), ingest, frames_u8.shape[1:3])
-        B, Hs, Ws, _ = frames_u8.shape
+        B, Hs, Ws = frames_u8.shape[:3]
         out = self._crops_to_identities(
             B, (Hs, Ws), dets, counts, (1.0, 1.0),
-            lambda meta, n_crops, y, amax: ops.roi_resize_u8(frames_u8, meta, n_crops, y, ingest.a, ingest.b,
-                                                             ingest.swap_rb, y_amax=amax),
+            lambda meta, n_crops, y, amax: nv12.roi_resize_src(frames_u8, meta, n_crops, y, ingest, y_amax=amax),
             max_per_frame=1, identify=False)
         return self._enrol(out, labels, B)
 
@@ -388,12 +386,12 @@ class PersonRecognition:
         m = self.model
         frames_u8, ingest = m._check_input_u8(frames_u8, ingest)
         m._sync_weights()
-        B, Hs, Ws, _ = frames_u8.shape
+        B, Hs, Ws = frames_u8.shape[:3]
         held = {}
         out_f = self.faces._crops_to_identities(
             B, (Hs, Ws), dets, counts, (1.0, 1.0),
-            lambda meta, n_crops, y, amax, warp: ops.roi_warp_u8(frames_u8, meta, n_crops, warp, y, ingest.a, ingest.b,
-                                                                 ingest.swap_rb, y_amax=amax),
+            lambda meta, n_crops, y, amax, warp: nv12.roi_warp_src(frames_u8, meta, n_crops, warp, y, ingest,
+                                                                  y_amax=amax),
             warp=self._rows(out_p, B, held), **kw)
         return out_f, held
 

@@ -32,6 +32,7 @@ from . import arch, ops
 from .engine import Engine
 from .ingest import FrameIngest
 from .modules import branch_trees
+from .nv12 import NV12Frames
 
 
 @dataclass
@@ -170,7 +171,10 @@ class CombinedModel:
     def _check_input_u8(self, x, ingest, sequence=False):
         """``sequence``: the caller's whole-frame ingest also takes a sequence of uint8 frames
         [Hs_i, Ws_i, 3] of different sizes; the crop stages do not."""
-        if isinstance(x, (list, tuple)):
+        if isinstance(x, NV12Frames):              # decoded video as the decoder leaves it (DESIGN.md §5m)
+            if not x.is_cuda:
+                raise ValueError(f"expected NV12 frames on a CUDA(HIP) device, got them on {x.device}")
+        elif isinstance(x, (list, tuple)):
             if not sequence:
                 raise ValueError("a sequence of frames of different sizes is taken by the whole-frame ingest only "
                                  "(forward_u8, forward_all_u8, FaceIdentifier): the crop stages resample from one "

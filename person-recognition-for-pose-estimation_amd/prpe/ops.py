@@ -12,7 +12,7 @@ import math
 
 import torch
 
-from ._lib import ACT, RES_NONE, BneckDesc, ConvDesc, IngestSrc, PrpeError, StemDesc, View, check, lib
+from ._lib import ACT, NV12, RES_NONE, BneckDesc, ConvDesc, IngestSrc, PrpeError, StemDesc, View, check, lib
 from .arch import VIT_IMG
 
 
@@ -955,6 +955,99 @@ def roi_warp_u8(frames, crop_meta, n_crops, warp, y, a=(1.0, 1.0, 1.0), b=(0.0, 
     check(lib().prpe_roi_warp_u8(C.byref(fv), crop_meta.data_ptr(), n_crops.data_ptr(), max_crops, warp.data_ptr(),
                                  _f3(what, "a", a), _f3(what, "b", b), int(bool(swap_rb)), C.byref(view(y)),
                                  _ptr(y_amax), _stream()), what)
+    return y
+
+
+# ------------------------------------------------------------------ NV12 frames in (csrc/nv12.hip)
+def _nv12_frames(what, frames):
+    """(prpe_nv12, coef) of a prpe.NV12Frames: the class has checked shapes, dtypes and strides;
+    the device is checked here, before the C ABI."""
+    from .nv12 import NV12Frames
+    if not isinstance(frames, NV12Frames):
+        raise ValueError(f"{what}: frames must be a prpe.NV12Frames, got {type(frames).__name__}")
+    if not frames.is_cuda:
+        raise ValueError(f"{what}: the planes must be HIP device tensors, got them on {frames.device}")
+    B, Hs, Ws = frames.shape
+    src = NV12(frames.y.data_ptr(), frames.uv.data_ptr(), B, Hs, Ws, frames.y.stride(0), frames.y.stride(1),
+               frames.uv.stride(0), frames.uv.stride(1))
+    return src, (C.c_int32 * 6)(*(int(v) for v in frames.coef))
+
+
+def nv12_to_rgb(frames, out, swap_rb=False):
+    """NV12 frames -> ``out``, uint8 [B, Hs, Ws, 3] on the device with 3 contiguous bytes per pixel
+    and any row and frame strides; ``swap_rb`` writes B, G, R (prpe_nv12_to_rgb, include/prpe.h)."""
+    what = "prpe_nv12_to_rgb"
+    src, coef = _nv12_frames(what, frames)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_cuda:
+        raise ValueError(f"{what}: out must be a uint8 device tensor")
+    if tuple(out.shape) != frames.shape + (3,) or out.stride(3) != 1 or out.stride(2) != 3 or \
+            out.stride(1) < 3 * frames.shape[2]:
+        raise ValueError(f"{what}: out must be {list(frames.shape + (3,))} with packed pixels (strides (.., .., 3, 1)), "
+                         f"got {list(out.shape)} strides {list(out.stride())}")
+    check(lib().prpe_nv12_to_rgb(C.byref(src), coef, int(bool(swap_rb)), out.data_ptr(), out.stride(0), out.stride(1),
+                                 _stream()), what)
+    return out
+
+
+def frame_ingest_nv12(frames, y, region, a, b, fill=(0.0, 0.0, 0.0), y_amax=None):
+    """``frame_ingest`` from NV12 frames (a prpe.NV12Frames): every tap converted as it is gathered;
+    the output channels are R, G, B (prpe_frame_ingest_nv12, include/prpe.h)."""
+    what = "prpe_frame_ingest_nv12"
+    src, coef = _nv12_frames(what, frames)
+    B = frames.shape[0]
+    if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 4):
+        raise ValueError(f"{what}: y must be a float32 device tensor [B, H, W, 4]")
+    if y.shape[0] != B or y.shape[3] != 4 or y.stride(3) != 1 or y.data_ptr() % 16 or \
+            any(s % 4 for s in y.stride()[:3]):
+        raise ValueError(f"{what}: y must be [{B}, H, W, 4] with 4 contiguous, 16-byte aligned "
+                         f"channels, got {list(y.shape)} strides {list(y.stride())}")
+    top, left, nh, nw = (int(v) for v in region)
+    if nh < 1 or nw < 1 or top < 0 or left < 0 or top + nh > y.shape[1] or left + nw > y.shape[2]:
+        raise ValueError(f"{what}: region {(top, left, nh, nw)} is empty or not inside {list(y.shape[1:3])}")
+    _check_slots(what, B, y_amax)
+    check(lib().prpe_frame_ingest_nv12(C.byref(src), coef, C.byref(view(y)), top, left, nh, nw, _f3(what, "a", a),
+                                       _f3(what, "b", b), _f3(what, "fill", fill), _ptr(y_amax), _stream()), what)
+    return y
+
+
+def crop_resize_nv12(frames, crop_meta, n_crops, crops, a=(1.0, 1.0, 1.0), b=(0.0, 0.0, 0.0)):
+    """``crop_resize_u8`` from NV12 frames (prpe_crop_resize_nv12, include/prpe.h)."""
+    what = "prpe_crop_resize_nv12"
+    src, coef = _nv12_frames(what, frames)
+    if not (isinstance(crop_meta, torch.Tensor) and crop_meta.dim() == 2):
+        raise ValueError(f"{what}: crop_meta must be [max_crops, {CROP_META_COLS}]")
+    max_crops = crop_meta.shape[0]
+    shape = (max_crops, VIT_IMG[0] + 2 * CROP_BORDER, VIT_IMG[1] + 2 * CROP_BORDER, 4)
+    _check_dev(what, "crop_meta", crop_meta, torch.float32, (max_crops, CROP_META_COLS))
+    _check_dev(what, "n_crops", n_crops, torch.int32, (1,))
+    _check_dev(what, "crops", crops, torch.float32, shape)
+    if max_crops < 1 or crops.data_ptr() % 16:
+        raise ValueError(f"{what}: crops must hold at least one slot and be 16-byte aligned")
+    check(lib().prpe_crop_resize_nv12(C.byref(src), coef, crop_meta.data_ptr(), n_crops.data_ptr(), max_crops,
+                                      _f3(what, "a", a), _f3(what, "b", b), crops.data_ptr(), _stream()), what)
+    return crops
+
+
+def roi_resize_nv12(frames, crop_meta, n_crops, y, a=(1.0, 1.0, 1.0), b=(0.0, 0.0, 0.0), y_amax=None):
+    """``roi_resize_u8`` from NV12 frames (prpe_roi_resize_nv12, include/prpe.h)."""
+    what = "prpe_roi_resize_nv12"
+    src, coef = _nv12_frames(what, frames)
+    max_crops = _roi_args(what, crop_meta, n_crops, y, y_amax)
+    check(lib().prpe_roi_resize_nv12(C.byref(src), coef, crop_meta.data_ptr(), n_crops.data_ptr(), max_crops,
+                                     C.byref(view(y)), _f3(what, "a", a), _f3(what, "b", b), _ptr(y_amax),
+                                     _stream()), what)
+    return y
+
+
+def roi_warp_nv12(frames, crop_meta, n_crops, warp, y, a=(1.0, 1.0, 1.0), b=(0.0, 0.0, 0.0), y_amax=None):
+    """``roi_warp_u8`` from NV12 frames (prpe_roi_warp_nv12, include/prpe.h)."""
+    what = "prpe_roi_warp_nv12"
+    src, coef = _nv12_frames(what, frames)
+    max_crops = _roi_args(what, crop_meta, n_crops, y, y_amax)
+    _check_dev(what, "warp", warp, torch.float32, (max_crops, WARP_COLS))
+    check(lib().prpe_roi_warp_nv12(C.byref(src), coef, crop_meta.data_ptr(), n_crops.data_ptr(), max_crops,
+                                   warp.data_ptr(), C.byref(view(y)), _f3(what, "a", a), _f3(what, "b", b),
+                                   _ptr(y_amax), _stream()), what)
     return y
 
 

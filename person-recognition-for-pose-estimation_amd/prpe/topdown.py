@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import torch
 
-from . import arch, ops
+from . import arch, nv12, ops
 from .postproc import non_max_suppression_padded
 
 
@@ -99,11 +99,10 @@ class TopDownPose:
         m = self.model
         frames_u8, ingest = m._check_input_u8(frames_u8, ingest)
         m._sync_weights()
-        B, Hs, Ws, _ = frames_u8.shape
+        B, Hs, Ws = frames_u8.shape[:3]
         return self._crops_to_keypoints(
             B, (Hs, Ws), dets, counts, 1.0,
-            lambda meta, n_crops, buf: ops.crop_resize_u8(frames_u8, meta, n_crops, buf, ingest.a, ingest.b,
-                                                          ingest.swap_rb))
+            lambda meta, n_crops, buf: nv12.crop_resize_src(frames_u8, meta, n_crops, buf, ingest))
 
     def _crops_to_keypoints(self, B, frame_hw, dets, counts, scale, resize):
         """crop list -> ``resize(meta, n_crops, buf)`` fills the crop buffer -> ViTPose -> keypoints
