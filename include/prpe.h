@@ -1125,6 +1125,97 @@ int prpe_roi_warp_nv12(const prpe_nv12* src, const int32_t* coef /* HOST: 6 */, 
                        const int32_t* n_crops, int32_t max_crops, const float* warp, const prpe_view* y,
                        const float* a, const float* b, float* y_amax /* optional */, void* stream);
 
+/*
+ * Annotated frames out (csrc/annotate.hip; additive to ABI 12): skeletons, person
+ * boxes and face redaction painted IN PLACE into the surface that goes to the encoder or the
+ * display, from the device arrays the crop, pose, face and tracking stages leave. The reference has
+ * no drawing code (a TODO in its callbacks.py); the semantics are this project's, chosen so that a
+ * host restatement is exact: one fp32 rounding per coordinate, everything after it in integers.
+ *
+ * The surface. prpe_annotate_nv12 writes the two planes its prpe_nv12 names: the struct's const
+ * is the reader's, the pointers are written through. prpe_annotate_u8 writes a prpe_view_u8 [B, H, W, 3]
+ * with any strides. Sides are 1..16384. Bytes between w and the pitch and rows below h are never
+ * written; a pixel no primitive covers is neither read nor written.
+ *
+ * Inputs, all device arrays read on the device except limbs:
+ *   crop_meta_p [max_p][8], n_p [1], keypoints [max_p][K][3] = (x, y, score), 1 <= K <= 64;
+ *   person_colour [max_p] int32: palette index, negative = the person is not drawn;
+ *   crop_meta_f [max_f][8], n_f [1], face_mode [max_f] int32 (1 pixelate, 2 fill, anything else
+ *   leave), face_colour [max_f] int32;
+ *   palette [n_colours][4] uint8, 4-byte aligned: (Y, U, V, 0) for the NV12 twin, (c0, c1, c2, 0)
+ *   for the u8 twin; a colour index is reduced modulo n_colours on the device (a negative
+ *   face_colour to the non-negative residue);
+ *   limbs: HOST, n_limbs <= 32 pairs of keypoint indices; it travels in the kernel arguments.
+ *   max_p and max_f are 0..2^20; with a capacity of 0 that list's pointers may be null.
+ *   A slot at or past its count (clamped to [0, capacity]) or with a frame index outside [0, B)
+ *   draws nothing.
+ * Scalars: box_t 0..16 (outline thickness; 0 = no boxes), limb_r and kp_r 0..16 (radii in pixels),
+ *   kp_thr, cell (even, 2..64), sx and sy (finite, positive: list coordinates -> surface pixels).
+ *
+ * Float to integer, the only floating point: a coordinate is q = rintf(v * s), one fp32 multiply,
+ *   then round half to even. A window (x0, y0, w, h = crop_meta[2..5]) is X0 = rintf(x0 * sx),
+ *   X1 = rintf((x0 + w) * sx) (the fp32 sum first, then the multiply; no contraction), Y likewise.
+ *   A primitive is skipped when one of its products is not finite or one of its rounded
+ *   coordinates is outside [-4096, 20479]; a window also when it is empty (X1 <= X0 or Y1 <= Y0).
+ *   Keypoint j counts when score >= kp_thr (a NaN score does not) and its two coordinates pass; a
+ *   limb needs both of its ends.
+ * Coverage, exact integers on pixel coordinates p = (x, y), 0 <= x < w, 0 <= y < h:
+ *   disc (c, r):       |p - c|^2 <= r^2
+ *   segment (a, b, r): with d = b - a, L2 = d.d: |p - a|^2 <= r^2, or |p - b|^2 <= r^2, or
+ *                      (L2 > 0 and 0 <= (p - a).d <= L2 and cross(d, p - a)^2 <= r^2 L2): round
+ *                      caps; L2 = 0 is a disc.
+ *   box outline:       inside [X0, X1) x [Y0, Y1) and not inside that rectangle shrunk by box_t on
+ *                      every side (a shrunk rectangle that is empty leaves the whole window).
+ *   Widths: a pixel is in [0, 16383] and a coordinate in [-4096, 20479], so every component of
+ *   p - a is within +-20479 < 2^15 and of d within +-24575 < 2^15. |p - a|^2, L2 and (p - a).d
+ *   are sums of two products below 2^30 in magnitude each, so below 2^31: they fit int32 (the
+ *   largest, 2 * 24575^2 = 1 207 861 250). cross(d, p - a) is bounded by 2 * 24575 * 20479 < 2^30.1;
+ *   it and its square (< 2^60.1) are formed in int64; r^2 L2 <= 256 * 2^31 = 2^39. Nothing
+ *   approaches 2^63.
+ * Priority: a pixel takes the highest layer that covers it, face redaction < boxes < limbs <
+ *   keypoint discs; inside a layer the lowest slot wins. A person's layers take palette
+ *   [person_colour]. Every painted byte is written exactly once; two runs give the same bytes.
+ * Redaction: a face's window clipped to the frame; overlapping faces by lowest slot. Mode 2 fills
+ *   with palette[face_colour]. Mode 1 pixelates: block side c = max(cell, 2 * ((side + 31) / 32)),
+ *   side = max(X1 - X0, Y1 - Y0) unclipped (at most 17 blocks per side); blocks anchored at
+ *   (X0 & ~1, Y0 & ~1); a block's value per channel is (sum + n / 2) / n over the block's samples
+ *   inside the frame (not clipped to the window). On NV12 luma is averaged over the block's luma
+ *   pixels and U, V over its chroma pairs; c and the anchor are even, so a pair lies in one block.
+ *   The means are taken by the first launch, from the surface as it is before anything is
+ *   painted, into means [max_f][17][17][4] uint8 (caller's, 4-byte aligned), and applied by the
+ *   second; stream order makes the in-place update safe.
+ * NV12 chroma: the pair (ci, cj) is painted exactly when luma pixel (2 ci, 2 cj) is, by the same
+ *   primitive's palette entry or block. So the painted luma pixels are the painted pixels of the
+ *   u8 twin on the same inputs.
+ * Workspaces: table, 16-byte aligned, at least prpe_annotate_table_bytes(max_p, max_f, K, n_limbs)
+ *   bytes (the integer primitives and their bounding boxes), and means. The library allocates
+ *   nothing and reads nothing back. prpe_annotate_geometry: out [4] = (tile h, tile w, super-tile
+ *   h, super-tile w), the paint launch's partition of the frame.
+ * -EINVAL, nothing launched and nothing written: a null dst, args, plane, palette, or list pointer
+ *   of a list with capacity > 0 (means included, for max_f > 0); limbs null with n_limbs > 0; a
+ *   side outside 1..16384 or n < 1; the plane and pitch refusals of the NV12 block above; c != 3
+ *   for the u8 twin; K outside 1..64; n_limbs outside 0..32 or a limb index outside [0, K); max_p
+ *   or max_f outside 0..2^20; box_t, limb_r or kp_r outside 0..16; cell odd or outside 2..64;
+ *   n_colours < 1; sx or sy not finite or not positive; a NaN kp_thr; a palette or means pointer
+ *   that is not 4-byte aligned; a table that is null, not 16-byte aligned or too small.
+ *   prpe_annotate_table_bytes returns -EINVAL for sizes outside the ranges above.
+ *   With max_p = max_f = 0 a call is legal and launches nothing.
+ */
+typedef struct prpe_annotate_args {
+  const float* crop_meta_p; const int32_t* n_p; const float* keypoints; const int32_t* person_colour;
+  const float* crop_meta_f; const int32_t* n_f; const int32_t* face_mode; const int32_t* face_colour;
+  const uint8_t* palette; const int32_t* limbs /* HOST: 2 * n_limbs */;
+  void* table; uint8_t* means;
+  int64_t table_bytes;
+  int32_t max_p, K, max_f, n_colours, n_limbs;
+  int32_t box_t, limb_r, kp_r, cell;
+  float kp_thr, sx, sy;
+} prpe_annotate_args;
+void prpe_annotate_geometry(int32_t* out /* HOST: 4 */);
+int64_t prpe_annotate_table_bytes(int32_t max_p, int32_t max_f, int32_t K, int32_t n_limbs);
+int prpe_annotate_nv12(const prpe_nv12* dst, const prpe_annotate_args* args, void* stream);
+int prpe_annotate_u8(const prpe_view_u8* dst, const prpe_annotate_args* args, void* stream);
+
 /* ABI version / build info. prpe_source_hash: sha256 (hex) of the sources the library was built
  * from (csrc/*.hip, csrc/*.h, include/prpe.h; computed by build.py), so a host binding can refuse
  * a library built from other sources than the ones beside it. */

@@ -7,6 +7,7 @@ Device work: hand-written HIP kernels in ../csrc behind the C ABI of include/prp
 (libprpe.so, loaded by prpe._lib). PyTorch-ROCm supplies device memory, streams and
 torch.distributed (RCCL) only.
 """
+from .annotate import Annotator  # noqa: F401
 from .arch import TASKS, state_dict_spec  # noqa: F401
 from .clusters import FaceClustering, FaceClusters  # noqa: F401
 from .evalsteps import CocoKeypointGT, PoseEvalStep, coco_keypoint_eval  # noqa: F401
@@ -22,6 +23,6 @@ from .verification import FaceVerification  # noqa: F401
 
 __all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "CocoKeypointGT", "coco_keypoint_eval",
            "TopDownPose", "FrameIngest", "NV12Frames", "FaceGallery", "FaceIdentifier", "FaceVerification",
-           "FaceClusters", "FaceClustering", "FaceCrops", "PersonRecognition", "PersonTracker",
+           "FaceClusters", "FaceClustering", "FaceCrops", "PersonRecognition", "PersonTracker", "Annotator",
            "non_max_suppression",
            "non_max_suppression_padded", "keypoints_from_heatmaps", "state_dict_spec", "TASKS"]

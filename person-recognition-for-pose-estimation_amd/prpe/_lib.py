@@ -42,6 +42,18 @@ class NV12(C.Structure):
                 ("y_sn", C.c_int64), ("y_sh", C.c_int64), ("uv_sn", C.c_int64), ("uv_sh", C.c_int64)]
 
 
+class AnnotateArgs(C.Structure):
+    """prpe_annotate_args: the lists, the palette, the workspaces and the scalars of prpe_annotate_nv12 / _u8."""
+    _fields_ = [("crop_meta_p", C.c_void_p), ("n_p", C.c_void_p), ("keypoints", C.c_void_p),
+                ("person_colour", C.c_void_p), ("crop_meta_f", C.c_void_p), ("n_f", C.c_void_p),
+                ("face_mode", C.c_void_p), ("face_colour", C.c_void_p), ("palette", C.c_void_p),
+                ("limbs", C.POINTER(C.c_int32)), ("table", C.c_void_p), ("means", C.c_void_p),
+                ("table_bytes", C.c_int64),
+                ("max_p", C.c_int32), ("K", C.c_int32), ("max_f", C.c_int32), ("n_colours", C.c_int32),
+                ("n_limbs", C.c_int32), ("box_t", C.c_int32), ("limb_r", C.c_int32), ("kp_r", C.c_int32),
+                ("cell", C.c_int32), ("kp_thr", C.c_float), ("sx", C.c_float), ("sy", C.c_float)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("x", View), ("y", View), ("res", View),
                 ("kh", C.c_int32), ("kw", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
@@ -147,6 +159,10 @@ SIGNATURES = {
     "prpe_roi_resize_nv12": (C.c_int, [_NP, _C6, _P, _P, _I, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
     "prpe_roi_warp_nv12": (C.c_int, [_NP, _C6, _P, _P, _I, _P, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float), _P,
                                      _P]),
+    "prpe_annotate_geometry": (None, [C.POINTER(C.c_int32)]),
+    "prpe_annotate_table_bytes": (C.c_int64, [_I, _I, _I, _I]),
+    "prpe_annotate_nv12": (C.c_int, [_NP, C.POINTER(AnnotateArgs), _P]),
+    "prpe_annotate_u8": (C.c_int, [_VP, C.POINTER(AnnotateArgs), _P]),
     "prpe_track_update": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _F, _I, C.POINTER(C.c_float), _F, _I,
                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "prpe_coco_kp_match_workspace_bytes": (C.c_int64, [_I]),

@@ -12,7 +12,7 @@ import math
 
 import torch
 
-from ._lib import ACT, NV12, RES_NONE, BneckDesc, ConvDesc, IngestSrc, PrpeError, StemDesc, View, check, lib
+from ._lib import ACT, NV12, RES_NONE, AnnotateArgs, BneckDesc, ConvDesc, IngestSrc, PrpeError, StemDesc, View, check, lib
 from .arch import VIT_IMG
 
 
@@ -1049,6 +1049,149 @@ def roi_warp_nv12(frames, crop_meta, n_crops, warp, y, a=(1.0, 1.0, 1.0), b=(0.0
                                    warp.data_ptr(), C.byref(view(y)), _f3(what, "a", a), _f3(what, "b", b),
                                    _ptr(y_amax), _stream()), what)
     return y
+
+
+# ------------------------------------------------------------------ annotated frames out (csrc/annotate.hip)
+ANNOTATE_MAX_SIDE = 16384
+ANNOTATE_MAX_K = 64
+ANNOTATE_MAX_LIMBS = 32
+ANNOTATE_MAX_R = 16                  # box_t, limb_r, kp_r
+ANNOTATE_BLOCKS = 17                 # pixelation blocks per side of a face, at most
+ANNOTATE_MAX_SLOTS = 1 << 20
+# the COCO skeleton: 19 limbs over the 17 keypoints
+COCO_LIMBS = ((15, 13), (13, 11), (16, 14), (14, 12), (11, 12), (5, 11), (6, 12), (5, 6), (5, 7), (6, 8), (7, 9),
+              (8, 10), (1, 2), (0, 1), (0, 2), (1, 3), (2, 4), (3, 5), (4, 6))
+
+
+def annotate_geometry():
+    """(tile h, tile w, super-tile h, super-tile w) of the paint launch (prpe_annotate_geometry)."""
+    out = (C.c_int32 * 4)()
+    lib().prpe_annotate_geometry(out)
+    return tuple(out)
+
+
+def annotate_table_bytes(max_p, max_f, K, n_limbs):
+    """Bytes of the primitive table of an annotate call (prpe_annotate_table_bytes)."""
+    n = lib().prpe_annotate_table_bytes(int(max_p), int(max_f), int(K), int(n_limbs))
+    if n < 0:
+        raise ValueError(f"prpe_annotate_table_bytes: max_p = {max_p}, max_f = {max_f} (0..{ANNOTATE_MAX_SLOTS}), "
+                         f"K = {K} (1..{ANNOTATE_MAX_K}), limbs = {n_limbs} (0..{ANNOTATE_MAX_LIMBS})")
+    return n
+
+
+def annotate_workspaces(max_p, max_f, K, n_limbs, device):
+    """(table, means) for an annotate call of these sizes: uint8 device tensors the caller keeps."""
+    table = torch.empty(max(annotate_table_bytes(max_p, max_f, K, n_limbs), 16), dtype=torch.uint8, device=device)
+    means = torch.empty(max(max_f, 1), ANNOTATE_BLOCKS, ANNOTATE_BLOCKS, 4, dtype=torch.uint8, device=device)
+    return table, means
+
+
+def _annotate_args(what, dev, hw, crop_meta_p, n_p, keypoints, person_colour, crop_meta_f, n_f, face_mode, face_colour,
+                   palette, limbs, table, means, box_t, limb_r, kp_r, kp_thr, cell, scale):
+    """prpe_annotate_args after every check the C side makes (and the shapes it cannot see)."""
+    def on_dev(name, t, dtype, shape):
+        _check_dev(what, name, t, dtype, shape)
+        if t.device != dev:
+            raise ValueError(f"{what}: {name} is on {t.device}, the surface on {dev}")
+
+    H, W = hw
+    if not (1 <= H <= ANNOTATE_MAX_SIDE and 1 <= W <= ANNOTATE_MAX_SIDE):
+        raise ValueError(f"{what}: the surface's sides must be in 1..{ANNOTATE_MAX_SIDE}, got {H} x {W}")
+    max_p = max_f = 0
+    K = 1
+    if crop_meta_p is not None:
+        if not (isinstance(crop_meta_p, torch.Tensor) and crop_meta_p.dim() == 2):
+            raise ValueError(f"{what}: crop_meta_p must be [max_p, {CROP_META_COLS}]")
+        if not (isinstance(keypoints, torch.Tensor) and keypoints.dim() == 3 and keypoints.shape[2] == 3):
+            raise ValueError(f"{what}: keypoints must be [max_p, K, 3]")
+        max_p, K = crop_meta_p.shape[0], keypoints.shape[1]
+        if not (1 <= max_p <= ANNOTATE_MAX_SLOTS and 1 <= K <= ANNOTATE_MAX_K):
+            raise ValueError(f"{what}: max_p = {max_p} (1..{ANNOTATE_MAX_SLOTS}), K = {K} (1..{ANNOTATE_MAX_K})")
+        on_dev("crop_meta_p", crop_meta_p, torch.float32, (max_p, CROP_META_COLS))
+        on_dev("n_p", n_p, torch.int32, (1,))
+        on_dev("keypoints", keypoints, torch.float32, (max_p, K, 3))
+        on_dev("person_colour", person_colour, torch.int32, (max_p,))
+    if crop_meta_f is not None:
+        if not (isinstance(crop_meta_f, torch.Tensor) and crop_meta_f.dim() == 2):
+            raise ValueError(f"{what}: crop_meta_f must be [max_f, {CROP_META_COLS}]")
+        max_f = crop_meta_f.shape[0]
+        if not 1 <= max_f <= ANNOTATE_MAX_SLOTS:
+            raise ValueError(f"{what}: max_f = {max_f} (1..{ANNOTATE_MAX_SLOTS})")
+        on_dev("crop_meta_f", crop_meta_f, torch.float32, (max_f, CROP_META_COLS))
+        on_dev("n_f", n_f, torch.int32, (1,))
+        on_dev("face_mode", face_mode, torch.int32, (max_f,))
+        on_dev("face_colour", face_colour, torch.int32, (max_f,))
+    if not (isinstance(palette, torch.Tensor) and palette.dim() == 2 and palette.shape[0] >= 1):
+        raise ValueError(f"{what}: palette must be [n_colours, 4] with at least one colour")
+    n_colours = palette.shape[0]
+    on_dev("palette", palette, torch.uint8, (n_colours, 4))
+    if palette.data_ptr() % 4:
+        raise ValueError(f"{what}: palette must be 4-byte aligned")
+    limbs = [(int(a), int(b)) for a, b in limbs] if max_p else []       # no persons: no skeleton to index
+    if len(limbs) > ANNOTATE_MAX_LIMBS or any(not (0 <= v < K) for ab in limbs for v in ab):
+        raise ValueError(f"{what}: at most {ANNOTATE_MAX_LIMBS} limbs with keypoint indices in [0, {K})")
+    box_t, limb_r, kp_r, cell, kp_thr = int(box_t), int(limb_r), int(kp_r), int(cell), float(kp_thr)
+    if not all(0 <= v <= ANNOTATE_MAX_R for v in (box_t, limb_r, kp_r)):
+        raise ValueError(f"{what}: box_t = {box_t}, limb_r = {limb_r}, kp_r = {kp_r} must be in 0..{ANNOTATE_MAX_R}")
+    if not 2 <= cell <= 64 or cell % 2:
+        raise ValueError(f"{what}: cell must be even and in 2..64, got {cell}")
+    sx, sy = (float(v) for v in ((scale, scale) if isinstance(scale, (int, float)) else scale))
+    if not (0.0 < sx < float("inf") and 0.0 < sy < float("inf")) or kp_thr != kp_thr:
+        raise ValueError(f"{what}: sx = {sx}, sy = {sy} must be finite and positive and kp_thr = {kp_thr} a number")
+    need = annotate_table_bytes(max_p, max_f, K, len(limbs))
+    tb = 0
+    if max_p + max_f:
+        if not (isinstance(table, torch.Tensor) and table.dtype == torch.uint8 and table.is_contiguous() and
+                table.device == dev and table.numel() >= need and table.data_ptr() % 16 == 0):
+            raise ValueError(f"{what}: table must be a contiguous uint8 tensor of at least {need} bytes on {dev}, "
+                             "16-byte aligned (ops.annotate_workspaces)")
+        tb = table.numel()
+    if max_f:
+        on_dev("means", means, torch.uint8, (max_f, ANNOTATE_BLOCKS, ANNOTATE_BLOCKS, 4))
+        if means.data_ptr() % 4:
+            raise ValueError(f"{what}: means must be 4-byte aligned")
+    flat = (C.c_int32 * max(2 * len(limbs), 1))(*(v for ab in limbs for v in ab))
+    args = AnnotateArgs(_ptr(crop_meta_p), _ptr(n_p), _ptr(keypoints), _ptr(person_colour), _ptr(crop_meta_f), _ptr(n_f),
+                        _ptr(face_mode), _ptr(face_colour), palette.data_ptr(), flat,
+                        table.data_ptr() if tb else None, means.data_ptr() if max_f else None, tb,
+                        max_p, K, max_f, n_colours, len(limbs), box_t, limb_r, kp_r, cell, kp_thr, sx, sy)
+    return args, flat
+
+
+def _annotate(what, call, dst, dev, hw, persons, faces, palette, limbs, table, means, kw):
+    crop_meta_p, n_p, keypoints, person_colour = persons if persons is not None else (None,) * 4
+    crop_meta_f, n_f, face_mode, face_colour = faces if faces is not None else (None,) * 4
+    args, keep = _annotate_args(what, dev, hw, crop_meta_p, n_p, keypoints, person_colour, crop_meta_f, n_f, face_mode,
+                                face_colour, palette, limbs, table, means, **kw)
+    check(call(C.byref(dst), C.byref(args), _stream()), what)
+    del keep
+
+
+def annotate_nv12(frames, palette, *, persons=None, faces=None, limbs=COCO_LIMBS, table=None, means=None, box_t=2,
+                  limb_r=1, kp_r=2, kp_thr=0.3, cell=8, scale=1.0):
+    """Paint skeletons, boxes and face redaction IN PLACE into NV12 frames (a prpe.NV12Frames;
+    prpe_annotate_nv12, include/prpe.h). ``persons`` = (crop_meta [max_p, 8], n_p [1] int32,
+    keypoints [max_p, K, 3], person_colour [max_p] int32; negative: not drawn) and ``faces`` =
+    (crop_meta [max_f, 8], n_f [1] int32, face_mode [max_f] int32: 1 pixelate, 2 fill,
+    face_colour [max_f] int32), either may be None. ``palette``: uint8 [n, 4] device = (Y, U, V, 0).
+    ``limbs``: pairs of keypoint indices (host). ``table``, ``means``: ops.annotate_workspaces.
+    ``scale``: (sx, sy), list coordinates -> surface pixels. No state, no host read."""
+    what = "prpe_annotate_nv12"
+    src, _ = _nv12_frames(what, frames)
+    _annotate(what, lib().prpe_annotate_nv12, src, frames.device, frames.shape[1:], persons, faces, palette, limbs, table,
+              means, dict(box_t=box_t, limb_r=limb_r, kp_r=kp_r, kp_thr=kp_thr, cell=cell, scale=scale))
+    return frames
+
+
+def annotate_u8(frames, palette, *, persons=None, faces=None, limbs=COCO_LIMBS, table=None, means=None, box_t=2,
+                limb_r=1, kp_r=2, kp_thr=0.3, cell=8, scale=1.0):
+    """``annotate_nv12`` on uint8 frames [B, H, W, 3] with any strides; ``palette`` holds
+    (c0, c1, c2, 0) in the frames' channel order (prpe_annotate_u8, include/prpe.h)."""
+    what = "prpe_annotate_u8"
+    fv = _u8_frames(what, frames)
+    _annotate(what, lib().prpe_annotate_u8, fv, frames.device, frames.shape[1:3], persons, faces, palette, limbs, table,
+              means, dict(box_t=box_t, limb_r=limb_r, kp_r=kp_r, kp_thr=kp_thr, cell=cell, scale=scale))
+    return frames
 
 
 # ------------------------------------------------------------------ tracking across frames (csrc/track.hip)

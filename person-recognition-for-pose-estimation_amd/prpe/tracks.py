@@ -5,6 +5,7 @@ prpe_track_update).
     tracker = PersonTracker(people, n_streams=4)          # four cameras
     out = tracker(frames)                                  # [B,3,H,W], frame b is camera b % 4; no host read
     persons = tracker.results(out)                         # per frame: box, keypoints, ident, track_id, ...
+    Annotator(colour_by="track")(frames_u8, out, coords_hw=frames.shape[2:])   # drawn on the device (prpe.annotate)
 
 ``PersonRecognition`` answers "who is standing how" for one frame; the tracker says that skeleton 3
 of this frame is skeleton 1 of the previous one, and keeps the name a face once gave a track over
