@@ -871,6 +871,87 @@ int prpe_track_update(const float* crop_meta_p, const int32_t* n_p, int32_t max_
                       int32_t* status, void* stream);
 
 /*
+ * Track-level face templates (csrc/tracktemplate.hip; additive to ABI 12): the
+ * embeddings of the faces of a track are summed into one template per track, and the template, not
+ * the single frame, is what the gallery is asked about. prpe_track_update names a track after its
+ * best-scoring frame; a template lets many frames that each stay under the threshold add up, and
+ * lets many frames outvote one false accept. The reference has no tracker and no gallery; the
+ * semantics are this project's, after the template protocol of AdaFace's video benchmarks (the sum
+ * of the un-normalised features, the feature norm being the quality weight).
+ *
+ * State (the caller's, persistent between calls, beside the tracker's; T = 32 slots per stream,
+ *   slot j of stream s belongs to track slot j of trk_meta):
+ *   tmpl_owner [S][32] int32: the track id the template belongs to, -1 none;
+ *   tmpl_sum [S][32][D] int64: fixed-point sums; tmpl_n [S][32] int32: the faces summed;
+ *   tmpl_ident [S][32] int64, tmpl_score [S][32]: the template's name and its score.
+ *   Fresh: owner -1, sums 0, n 0, ident -1, score -inf.
+ *
+ * track_template_update runs after prpe_track_update of the same call, on the same person list
+ *   (crop_meta_p [max_p][8], n_p [1]), track_id [max_p] as track_update wrote it, person_face
+ *   [max_p] int32 as prpe_face_person_match leaves it, the face list (embeddings [max_f][D] with a
+ *   row stride in elements, norms [max_f], n_f [1]; counts are clamped to [0, capacity]),
+ *   frame_stream [B], and trk_meta [S][32][8] as track_update left it (read only).
+ *   Per slot (s, j), id = the int32 bits of trk_meta[s][j][0]:
+ *   1. id < 0: the slot's template is cleared to the fresh values.
+ *   2. tmpl_owner != id: the slot was reused; it is cleared, then tmpl_owner = id.
+ *   3. Person slot i < n_p is a candidate when its frame b is in [0, B), frame_stream[b] == s,
+ *      track_id[i] == id and f = person_face[i] is in [0, n_f). Ids are unique within a stream for
+ *      the life of the state, so persons of a track that died earlier in the same call match no
+ *      slot and are dropped, and a track that took over a freed slot in the same call starts from
+ *      zero. The candidates are taken in ascending i. A candidate contributes when norms[f] is
+ *      finite, >= min_norm and < 2^15, all D elements of embeddings[f] are finite, and
+ *      tmpl_n < 2^20; otherwise it is skipped whole. A contribution:
+ *        tmpl_sum[d] += llrintf(p_d * 2^24), p_d = w * embeddings[f][d] (one fp32 product, nothing
+ *        fused; the scaling is exact), w = norms[f] with weight_mode 0 and 1 with weight_mode 1;
+ *        tmpl_n += 1.
+ *      Embedding rows are unit rows: |p_d| < 2^15, a term is below 2^39 in magnitude and 2^20 of
+ *      them stay below 2^59. (A finite element so large that p_d * 2^24 leaves int64 gives an
+ *      unspecified sum.) Integer adds commute: the sums equal a host sum exactly, whatever the
+ *      order, the split into calls, or the slot order of persons and faces. A face slot that two
+ *      persons of a track name contributes twice.
+ *   4. A slot that took at least one contribution is DIRTY. The dirty slots in ascending
+ *      s * 32 + j form the list: dirty_rows [max_q] int32 (the slot s * 32 + j; -1 at and past
+ *      n_dirty), n_dirty [1], dirty_pos [S][32] int32 (the slot's position in the list, -1 for a
+ *      slot that is not dirty), queries [max_q][D] fp32 with
+ *      queries[r][d] = (float)((double)tmpl_sum[d] * 2^-24), rows at and past n_dirty zero.
+ *      max_q >= min(S * 32, max_f) is required: every dirty slot has a face of its own unless two
+ *      tracks name one face slot, which prpe_face_person_match never produces. Should it happen
+ *      and the list be full, n_dirty = max_q, and the slots past it get their position in
+ *      dirty_pos (>= max_q) but no row: they keep their name until they are dirty again.
+ *   Two launches in stream order: the sums (one workgroup per slot; a state row is written once,
+ *   and only when it is cleared or dirty), then the list. No atomics, no workspace.
+ *   The caller then runs prpe_gallery_topk (k = 1, with labels, threshold and ident) on
+ *   queries [max_q][D]; it normalises the queries itself.
+ *
+ * track_template_assign takes that search's ident [max_q] int64 and score [max_q], n_dirty,
+ *   dirty_rows and dirty_pos, the state and the person list: for the slot at list position
+ *   r < n_dirty, (tmpl_ident, tmpl_score) = (ident[r], score[r]); every other slot keeps what it
+ *   had. Per person slot: template_ident [max_p] int64, template_score [max_p], template_faces
+ *   [max_p] int32 = the (tmpl_ident, tmpl_score, tmpl_n) after this update of the slot j of its
+ *   stream with trk_meta[s][j].id == track_id[i] (a person whose track is live after the call);
+ *   every other slot of the person list gets (-1, -inf, 0). One launch: a thread that serves a
+ *   person reads the state only of slots that are in no list.
+ * -EINVAL, nothing launched and nothing written: a null pointer; B, S, max_p (or, for update,
+ *   max_f) below 1; S above 4096 (each of the S workgroups that number the list reads the S * 32
+ *   flags of all of them: 2^29 loads at the limit) or max_p above 2^30; update: D not a multiple of 32 in [32, 512],
+ *   a row stride below D, max_q below min(S * 32, max_f), weight_mode outside {0, 1}, a NaN
+ *   min_norm; assign: max_q below 1.
+ */
+int prpe_track_template_update(const float* crop_meta_p, const int32_t* n_p, int32_t max_p, const int32_t* track_id,
+                               const int32_t* person_face, const float* embeddings, int64_t emb_row_stride,
+                               const float* norms, const int32_t* n_f, int32_t max_f, int32_t D,
+                               const int32_t* frame_stream, int32_t B, int32_t S, const float* trk_meta,
+                               int32_t weight_mode, float min_norm, int32_t* tmpl_owner, int64_t* tmpl_sum,
+                               int32_t* tmpl_n, int64_t* tmpl_ident, float* tmpl_score, int32_t* dirty_rows,
+                               int32_t* n_dirty, int32_t* dirty_pos, float* queries, int32_t max_q, void* stream);
+int prpe_track_template_assign(const float* crop_meta_p, const int32_t* n_p, int32_t max_p, const int32_t* track_id,
+                               const int32_t* frame_stream, int32_t B, int32_t S, const float* trk_meta,
+                               const int64_t* ident, const float* score, const int32_t* n_dirty,
+                               const int32_t* dirty_rows, const int32_t* dirty_pos, int32_t max_q,
+                               const int32_t* tmpl_n, int64_t* tmpl_ident, float* tmpl_score, int64_t* template_ident,
+                               float* template_score, int32_t* template_faces, void* stream);
+
+/*
  * COCO keypoint evaluation of an epoch's pose records (csrc/cocoeval.hip): what
  * pycocotools' COCOeval(gt, dt, 'keypoints') computes in evaluate(), accumulate() and summarize(),
  * in fp64 and in its operation order, on the records prpe_pose_coco_records left on the device.

@@ -165,6 +165,10 @@ SIGNATURES = {
     "prpe_annotate_u8": (C.c_int, [_VP, C.POINTER(AnnotateArgs), _P]),
     "prpe_track_update": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _F, _I, C.POINTER(C.c_float), _F, _I,
                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "prpe_track_template_update": (C.c_int, [_P, _P, _I, _P, _P, _P, _L, _P, _P, _I, _I, _P, _I, _I, _P, _I, _F,
+                                             _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "prpe_track_template_assign": (C.c_int, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P,
+                                             _P, _P]),
     "prpe_coco_kp_match_workspace_bytes": (C.c_int64, [_I]),
     "prpe_coco_kp_match": (C.c_int, [_P, _P, _P, _L, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -1261,6 +1261,118 @@ def track_update(crop_meta_p, n_p, keypoints, person_ident, person_score, frame_
     return track_id, track_hits, track_ident, track_iscore, status
 
 
+# ------------------------------------------------------------------ track-level face templates (csrc/tracktemplate.hip)
+TEMPLATE_WEIGHTS = {"norm": 0, "uniform": 1}
+TEMPLATE_SCALE_BITS = 24             # a contribution is llrintf(w * e * 2^24)
+TEMPLATE_MAX_NORM = 32768.0          # a face whose norm is at or above 2^15 is skipped
+TEMPLATE_MAX_FACES = 1 << 20         # faces a template sums at most
+TEMPLATE_MAX_STREAMS = 4096          # the list launch reads S * 32 flags in each of its S workgroups
+
+
+def _template_persons(what, crop_meta_p, n_p, track_id, frame_stream, trk_meta):
+    if not (isinstance(crop_meta_p, torch.Tensor) and crop_meta_p.dim() == 2):
+        raise ValueError(f"{what}: crop_meta_p must be [slots, {CROP_META_COLS}]")
+    if not (isinstance(frame_stream, torch.Tensor) and frame_stream.dim() == 1):
+        raise ValueError(f"{what}: frame_stream must be [B]")
+    if not (isinstance(trk_meta, torch.Tensor) and trk_meta.dim() == 3):
+        raise ValueError(f"{what}: trk_meta must be [S, {TRACK_SLOTS}, 8]")
+    P, B, S = crop_meta_p.shape[0], frame_stream.shape[0], trk_meta.shape[0]
+    _check_dev(what, "crop_meta_p", crop_meta_p, torch.float32, (P, CROP_META_COLS))
+    _check_dev(what, "n_p", n_p, torch.int32, (1,))
+    _check_dev(what, "track_id", track_id, torch.int32, (P,))
+    _check_dev(what, "frame_stream", frame_stream, torch.int32, (B,))
+    _check_dev(what, "trk_meta", trk_meta, torch.float32, (S, TRACK_SLOTS, 8))
+    if P < 1 or B < 1 or not 1 <= S <= TEMPLATE_MAX_STREAMS or P > 1 << 30:
+        raise ValueError(f"{what}: P = {P}, frames = {B}, streams = {S}")
+    return P, B, S
+
+
+def track_template_update(crop_meta_p, n_p, track_id, person_face, embeddings, norms, n_f, frame_stream, trk_meta, *,
+                          tmpl_owner, tmpl_sum, tmpl_n, tmpl_ident, tmpl_score, dirty_rows, n_dirty, dirty_pos, queries,
+                          weight="norm", min_norm=0.0):
+    """The faces of this call's persons into their tracks' templates (prpe_track_template_update,
+    include/prpe.h), after ``track_update`` of the same call: the person list (crop_meta_p [P, 8],
+    n_p [1], track_id [P] int32, person_face [P] int32), the face list (embeddings [F, D] float32 with
+    unit stride along D and any row stride >= D, norms [F], n_f [1]), frame_stream [B] int32 and
+    trk_meta [S, 32, 8] (read only), against the caller's template state (tmpl_owner, tmpl_n [S, 32]
+    int32, tmpl_sum [S, 32, D] int64, tmpl_ident [S, 32] int64, tmpl_score [S, 32]), updated in place
+    -> the list of the templates that changed: dirty_rows [Q] int32, n_dirty [1], dirty_pos [S, 32]
+    int32 and queries [Q, D] float32 (rows at and past n_dirty zero), Q >= min(S * 32, F).
+    ``weight``: "norm" (a face weighs its feature norm) or "uniform"; a face whose norm is below
+    ``min_norm`` is skipped. No host read."""
+    what = "prpe_track_template_update"
+    P, B, S = _template_persons(what, crop_meta_p, n_p, track_id, frame_stream, trk_meta)
+    if weight not in TEMPLATE_WEIGHTS:
+        raise ValueError(f"{what}: weight must be one of {sorted(TEMPLATE_WEIGHTS)}, got {weight!r}")
+    min_norm = float(min_norm)
+    if min_norm != min_norm:
+        raise ValueError(f"{what}: min_norm must be a number")
+    e = embeddings
+    if not (isinstance(e, torch.Tensor) and e.is_cuda and e.dtype == torch.float32 and e.dim() == 2 and e.shape[0] >= 1
+            and (e.shape[1] == 1 or e.stride(1) == 1) and e.stride(0) >= e.shape[1]):
+        raise ValueError(f"{what}: embeddings must be a float32 device tensor [F >= 1, D] with unit stride along D and "
+                         f"a row stride of at least D")
+    F, D = e.shape
+    _gallery_dim(what, D)
+    T = TRACK_SLOTS
+    _check_dev(what, "person_face", person_face, torch.int32, (P,))
+    _check_dev(what, "norms", norms, torch.float32, (F,))
+    _check_dev(what, "n_f", n_f, torch.int32, (1,))
+    _check_dev(what, "tmpl_owner", tmpl_owner, torch.int32, (S, T))
+    _check_dev(what, "tmpl_sum", tmpl_sum, torch.int64, (S, T, D))
+    _check_dev(what, "tmpl_n", tmpl_n, torch.int32, (S, T))
+    _check_dev(what, "tmpl_ident", tmpl_ident, torch.int64, (S, T))
+    _check_dev(what, "tmpl_score", tmpl_score, torch.float32, (S, T))
+    if not (isinstance(queries, torch.Tensor) and queries.dim() == 2 and queries.shape[0] >= min(S * T, F)):
+        raise ValueError(f"{what}: queries must be [Q >= min(S * {T}, F) = {min(S * T, F)}, D]")
+    Q = queries.shape[0]
+    _check_dev(what, "queries", queries, torch.float32, (Q, D))
+    _check_dev(what, "dirty_rows", dirty_rows, torch.int32, (Q,))
+    _check_dev(what, "n_dirty", n_dirty, torch.int32, (1,))
+    _check_dev(what, "dirty_pos", dirty_pos, torch.int32, (S, T))
+    check(lib().prpe_track_template_update(crop_meta_p.data_ptr(), n_p.data_ptr(), P, track_id.data_ptr(),
+                                           person_face.data_ptr(), e.data_ptr(), e.stride(0), norms.data_ptr(),
+                                           n_f.data_ptr(), F, D, frame_stream.data_ptr(), B, S, trk_meta.data_ptr(),
+                                           TEMPLATE_WEIGHTS[weight], min_norm, tmpl_owner.data_ptr(),
+                                           tmpl_sum.data_ptr(), tmpl_n.data_ptr(), tmpl_ident.data_ptr(),
+                                           tmpl_score.data_ptr(), dirty_rows.data_ptr(), n_dirty.data_ptr(),
+                                           dirty_pos.data_ptr(), queries.data_ptr(), Q, _stream()), what)
+    return dirty_rows, n_dirty, dirty_pos, queries
+
+
+def track_template_assign(crop_meta_p, n_p, track_id, frame_stream, trk_meta, ident, score, n_dirty, dirty_rows,
+                          dirty_pos, *, tmpl_n, tmpl_ident, tmpl_score, template_ident, template_score, template_faces):
+    """The gallery's answer for the templates that changed, back into the state and out to the persons
+    (prpe_track_template_assign, include/prpe.h): ident [Q] int64 and score [Q] are the search's
+    result on ``queries`` of ``track_template_update``, whose n_dirty, dirty_rows and dirty_pos come
+    along; tmpl_ident and tmpl_score take them at the listed slots. Per person slot: template_ident
+    [P] int64, template_score [P] and template_faces [P] int32, (-1, -inf, 0) for a person without
+    a live track. No host read."""
+    what = "prpe_track_template_assign"
+    P, B, S = _template_persons(what, crop_meta_p, n_p, track_id, frame_stream, trk_meta)
+    if not (isinstance(ident, torch.Tensor) and ident.dim() == 1 and ident.shape[0] >= 1):
+        raise ValueError(f"{what}: ident must be [Q >= 1]")
+    Q, T = ident.shape[0], TRACK_SLOTS
+    _check_dev(what, "ident", ident, torch.int64, (Q,))
+    _check_dev(what, "score", score, torch.float32, (Q,))
+    _check_dev(what, "n_dirty", n_dirty, torch.int32, (1,))
+    _check_dev(what, "dirty_rows", dirty_rows, torch.int32, (Q,))
+    _check_dev(what, "dirty_pos", dirty_pos, torch.int32, (S, T))
+    _check_dev(what, "tmpl_n", tmpl_n, torch.int32, (S, T))
+    _check_dev(what, "tmpl_ident", tmpl_ident, torch.int64, (S, T))
+    _check_dev(what, "tmpl_score", tmpl_score, torch.float32, (S, T))
+    _check_dev(what, "template_ident", template_ident, torch.int64, (P,))
+    _check_dev(what, "template_score", template_score, torch.float32, (P,))
+    _check_dev(what, "template_faces", template_faces, torch.int32, (P,))
+    check(lib().prpe_track_template_assign(crop_meta_p.data_ptr(), n_p.data_ptr(), P, track_id.data_ptr(),
+                                           frame_stream.data_ptr(), B, S, trk_meta.data_ptr(), ident.data_ptr(),
+                                           score.data_ptr(), n_dirty.data_ptr(), dirty_rows.data_ptr(),
+                                           dirty_pos.data_ptr(), Q, tmpl_n.data_ptr(), tmpl_ident.data_ptr(),
+                                           tmpl_score.data_ptr(), template_ident.data_ptr(), template_score.data_ptr(),
+                                           template_faces.data_ptr(), _stream()), what)
+    return template_ident, template_score, template_faces
+
+
 # ------------------------------------------------------------------ face identification (csrc/gallery.hip)
 GALLERY_MAX_K = 8
 GALLERY_MAX_DIM = 512
