@@ -1132,6 +1132,89 @@ int prpe_cluster_centroids(const float* a, int64_t a_row_stride, int32_t N, int3
                            void* stream);
 
 /*
+ * Open-set 1:N identification evaluation: per probe the best enrolled row of its own label (its
+ * mate), the best row of any other label, the rank of the first mate, and from these the
+ * histograms behind DIR / FNIR / FPIR and the CMC (csrc/identeval.hip).
+ * prpe_pair_hist's GEMM with a third epilogue: the score matrix never reaches memory. The reference
+ * has no such code; the semantics are this project's. The library allocates nothing; no host
+ * sync. Additive to ABI 12.
+ *
+ * Operands: as for prpe_pair_hist. Probes a [M][D] and gallery b [N][D], fp32 rows that are ALREADY
+ *   L2-normalised (prpe_gallery_enrol's output). Row strides in elements, >= D and a multiple of 4;
+ *   a and b 16-byte aligned; D a multiple of 32 in [32, 512]; 1 <= M, N <= 2^24. a_labels [M] /
+ *   b_labels [N] int64; a_valid [M] / b_valid [N] optional bytes. The uint64 arrays are 8-byte
+ *   aligned.
+ * score(i, j): prpe_pair_hist's, prpe_pair_link's and prpe_gallery_topk's bits, (a0 + a1) + (a2 + a3),
+ *   a_e the chain acc = fma(x[c], y[c], acc) over the columns c with c % 4 == e in ascending order.
+ * Which rows take part: a probe when its valid byte is non-zero and its label >= 0; a gallery row
+ *   when its valid byte is non-zero (its label is only compared, as prpe_gallery_topk does: a
+ *   negative one equals no probe's). A (probe, row) combination of rows that take part is a
+ *   candidate when its score is finite; otherwise it adds 1 to skipped[0].
+ * Modes: b != NULL is cross mode: every probe against every gallery row; candidate row j of b has
+ *   the number b_row0 + j (b_row0 >= 0, b_row0 + N <= 2^31 - 1), so a gallery may be passed in
+ *   several row ranges into the same outputs. b == NULL is self mode, leave-one-out on one
+ *   labelled set: every row of a is a probe against all other rows (i != j); b_labels and b_valid
+ *   must be NULL and b_row0 0 (b_row_stride and N are ignored). Only the upper triangle of score
+ *   tiles is computed: a pair (i, j), i < j, serves probe i with row j and probe j with row i
+ *   (score(i, j) == score(j, i)). skipped counts both directions. M = 1 is legal and finds nothing.
+ * Order: the candidates of a probe are ordered as prpe_gallery_topk orders them, score descending,
+ *   then row ascending, by one key per candidate:
+ *     key = image(score) << 32 | (0xFFFFFFFF - row),
+ *   image(s) = u ^ (u >> 31 ? 0xFFFFFFFF : 0x80000000) with u the bits of s after -0 became +0.
+ *   A larger key is an earlier candidate; no candidate has key 0, which means "none".
+ * prpe_ident_best (pass 1): mate_key[i] = the largest key over the candidates of probe i whose label
+ *   equals the probe's, non_key[i] = the largest over the others. 64-bit atomic maxima into the
+ *   caller-zeroed [M] arrays (one per probe row and tile side, after a reduction in registers and
+ *   LDS); the slots of probes that take no part are not written. A max commutes: two runs, any
+ *   grid and any split of the gallery give the same bits. skipped [1] is ADDED to.
+ * prpe_ident_rank (pass 2): the same product, reading mate_key (complete: of the whole gallery).
+ *   rank_minus_1[i], caller-zeroed int32 [M], is ADDED the number of non-mate candidates of probe i
+ *   whose key is greater than mate_key[i]; a probe without a mate adds nothing. The rank counts
+ *   gallery ROWS, not identities: rank r means the first mate is the r-th entry of an unbounded
+ *   search.
+ * prpe_ident_finish: one small launch over the M probes. Writes
+ *     mate_score, non_score fp32 [M] and mate_row, non_row int32 [M]: the keys decoded (-0 reads
+ *       +0); -inf and -1 for an empty slot and for a probe that takes no part;
+ *     rank int32 [M]: 0 when the probe takes no part or has no mate, else rank_minus_1 + 1.
+ *   and ADDS (64-bit atomic adds; the caller zeroes them, and may pass the probes in several calls)
+ *     hist uint64 [3][nbins], prpe_pair_hist's bins (nbins in {256 .. 4096}, h = nbins / 2,
+ *       bin(s) = clamp((int)floorf(s * h) + h, 0, nbins - 1)):
+ *       row 0: the mated probes with mate_key > non_key (rank 1), binned by mate_score;
+ *       row 1: the mated probes with rank > 1, binned by non_score (the wrong label an identify
+ *              would return);
+ *       row 2: the probes that take part and have no mate (strangers to the gallery) but at least
+ *              one candidate, binned by non_score.
+ *       Bin edges are exact in fp32, so for every edge t = edge_b the sums of rows 0, 1 and 2 over
+ *       the bins >= b are EXACTLY the probes for which an identify at threshold t returns the right
+ *       label, a wrong label, and any label for a stranger.
+ *     rank_hist uint64 [PRPE_IDENT_RANKS + 1]: every mated probe in slot min(rank, R + 1) - 1.
+ *     counts uint64 [4]: mated probes; non-mated probes (those without any candidate included);
+ *       probes left out; non-mated probes without any candidate. [0] + [1] + [2] == M.
+ *   rank_minus_1 is optional (pass 2 not run): then rank is 1 for mate_key > non_key, -1 for the
+ *   other mated probes, rank_hist must be NULL and is not written.
+ * -EINVAL, nothing launched and nothing written: a null a, a_labels, mate_key, non_key, skipped,
+ *   rank_minus_1 (rank) or output; b_labels, b_valid or a non-zero b_row0 without b; b without
+ *   b_labels; M (or, with b, N) below 1 or above 2^24; b_row0 < 0 or b_row0 + N > 2^31 - 1; D not a
+ *   multiple of 32 in [32, 512]; a row stride below D or not a multiple of 4; a or b not 16-byte
+ *   aligned; a uint64 array not 8-byte aligned; nbins outside the list; rank_hist without
+ *   rank_minus_1 or rank_minus_1 without rank_hist.
+ */
+#define PRPE_IDENT_RANKS 64
+int prpe_ident_best(const float* a, int64_t a_row_stride, int32_t M, const int64_t* a_labels,
+                    const uint8_t* a_valid /* optional */, const float* b /* NULL: self mode */, int64_t b_row_stride,
+                    int32_t N, const int64_t* b_labels, const uint8_t* b_valid /* optional */, int32_t b_row0,
+                    int32_t D, uint64_t* mate_key, uint64_t* non_key, uint64_t* skipped, void* stream);
+int prpe_ident_rank(const float* a, int64_t a_row_stride, int32_t M, const int64_t* a_labels,
+                    const uint8_t* a_valid /* optional */, const float* b /* NULL: self mode */, int64_t b_row_stride,
+                    int32_t N, const int64_t* b_labels, const uint8_t* b_valid /* optional */, int32_t b_row0,
+                    int32_t D, const uint64_t* mate_key, int32_t* rank_minus_1, void* stream);
+int prpe_ident_finish(int32_t M, const int64_t* a_labels, const uint8_t* a_valid /* optional */,
+                      const uint64_t* mate_key, const uint64_t* non_key, const int32_t* rank_minus_1 /* optional */,
+                      int32_t nbins, float* mate_score, int32_t* mate_row, float* non_score, int32_t* non_row,
+                      int32_t* rank, uint64_t* hist, uint64_t* rank_hist /* with rank_minus_1 */, uint64_t* counts,
+                      void* stream);
+
+/*
  * NV12 frames in (csrc/nv12.hip; additive to ABI 12): what a hardware video decoder
  * hands over -- a full-resolution luma plane, a half-resolution plane of interleaved chroma pairs
  * and a row pitch wider than the picture -- read by the stem and crop stages themselves, with no

@@ -13,6 +13,7 @@ from .clusters import FaceClustering, FaceClusters  # noqa: F401
 from .evalsteps import CocoKeypointGT, PoseEvalStep, coco_keypoint_eval  # noqa: F401
 from .faces import FaceCrops, PersonRecognition  # noqa: F401
 from .gallery import FaceGallery, FaceIdentifier  # noqa: F401
+from .identification import IdentificationEval  # noqa: F401
 from .ingest import FrameIngest  # noqa: F401
 from .model import CombinedModel, PoseOutput  # noqa: F401
 from .nv12 import NV12Frames  # noqa: F401
@@ -23,6 +24,7 @@ from .verification import FaceVerification  # noqa: F401
 
 __all__ = ["CombinedModel", "PoseOutput", "PoseEvalStep", "CocoKeypointGT", "coco_keypoint_eval",
            "TopDownPose", "FrameIngest", "NV12Frames", "FaceGallery", "FaceIdentifier", "FaceVerification",
+           "IdentificationEval",
            "FaceClusters", "FaceClustering", "FaceCrops", "PersonRecognition", "PersonTracker", "Annotator",
            "non_max_suppression",
            "non_max_suppression_padded", "keypoints_from_heatmaps", "state_dict_spec", "TASKS"]

@@ -145,6 +145,9 @@ SIGNATURES = {
     "prpe_pair_link": (C.c_int, [_P, _L, _I, _P, _I, _F, _I, _P, _P, _L, _P]),
     "prpe_cluster_finish": (C.c_int, [_I, _P, _I, _P, _P, _L, _P, _P, _P, _P, _I, _P, _P]),
     "prpe_cluster_centroids": (C.c_int, [_P, _L, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "prpe_ident_best": (C.c_int, [_P, _L, _I, _P, _P, _P, _L, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "prpe_ident_rank": (C.c_int, [_P, _L, _I, _P, _P, _P, _L, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "prpe_ident_finish": (C.c_int, [_I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "prpe_roi_select": (C.c_int, [_P, _P, _I, _I, _F, _I, _F, _F, _F, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P]),
     "prpe_roi_resize": (C.c_int, [_VP, _P, _P, _I, _VP, _P, _P]),
     "prpe_roi_resize_u8": (C.c_int, [_VP, _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _VP, _P, _P]),

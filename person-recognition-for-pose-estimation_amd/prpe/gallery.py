@@ -9,7 +9,9 @@
   of DESIGN.md §5k, which returns the same bits and is faster for many queries per call.
 * ``FaceIdentifier`` — frames -> trunk -> AdaFace embedding -> ``add`` / ``identify``; it calls the
   engine directly, so the model's ``set_task`` state is left alone. ``calibrate`` takes its
-  threshold from a ``FaceVerification`` (prpe/verification.py) at a target FAR.
+  threshold from a ``FaceVerification`` (prpe/verification.py) at a target FAR,
+  ``calibrate_fpir`` from an ``IdentificationEval`` (prpe/identification.py, §5p) at a target
+  false-positive identification rate on the gallery as enrolled.
 
 The reference names the task (scripts/modify_models.py:331) but has no gallery code; the semantics
 are stated in include/prpe.h.
@@ -157,6 +159,15 @@ class FaceIdentifier:
         (a ``prpe.FaceVerification``) are accepted at a rate of at most ``far``; returns that row of
         ``verification.compute`` (threshold, tar, false_accepts, true_accepts). One host read."""
         row = verification.compute(far=(far,))["at_far"][0]
+        self.threshold = float(row["threshold"])
+        return row
+
+    def calibrate_fpir(self, evaluation, fpir: float):
+        """Set ``threshold`` to the lowest bin edge at which the strangers among ``evaluation``'s
+        probes (a ``prpe.IdentificationEval`` on the enrolled gallery) are named at a rate of at most
+        ``fpir`` per identify call; returns that row of ``evaluation.compute`` (threshold, dir, fnir,
+        false_positives, right_names, wrong_names). One host read."""
+        row = evaluation.compute(fpir=(fpir,), cmc=False)["at_fpir"][0]
         self.threshold = float(row["threshold"])
         return row
 

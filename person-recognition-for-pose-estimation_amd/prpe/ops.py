@@ -1683,3 +1683,101 @@ def cluster_centroids(a, *, cluster, n_clusters, sums, centroids):
     check(lib().prpe_cluster_centroids(a.data_ptr(), lda, N, D, cluster.data_ptr(), n_clusters.data_ptr(), max_clusters,
                                        sums.data_ptr(), centroids.data_ptr(), _stream()), what)
     return sums, centroids
+
+
+# ------------------------------------------------------------------ identification evaluation (csrc/identeval.hip)
+IDENT_RANKS = 64                     # PRPE_IDENT_RANKS: rank_hist has IDENT_RANKS + 1 slots
+
+
+def _ident_operands(what, a, a_labels, b, b_labels, a_valid, b_valid, b_row0):
+    """The operand checks ``ident_best`` and ``ident_rank`` share; returns the leading arguments
+    of the C call and M."""
+    if not (isinstance(a, torch.Tensor) and a.dim() == 2):
+        raise ValueError(f"{what}: a must be [M, D]")
+    D = a.shape[1]
+    _gallery_dim(what, D)
+    M, lda = _pair_rows(what, "a", a, D)
+    _check_dev(what, "a_labels", a_labels, torch.int64, (M,))
+    if a_valid is not None:
+        _check_dev(what, "a_valid", a_valid, torch.uint8, (M,))
+    N, ldb, b_row0 = 0, 0, int(b_row0)
+    if b is None:
+        if b_labels is not None or b_valid is not None or b_row0 != 0:
+            raise ValueError(f"{what}: b_labels, b_valid and b_row0 need b")
+    else:
+        N, ldb = _pair_rows(what, "b", b, D)
+        _check_dev(what, "b_labels", b_labels, torch.int64, (N,))
+        if b_valid is not None:
+            _check_dev(what, "b_valid", b_valid, torch.uint8, (N,))
+        if not 0 <= b_row0 <= 2 ** 31 - 1 - N:
+            raise ValueError(f"{what}: b_row0 must lie in [0, 2^31 - 1 - N], got {b_row0}")
+    return (a.data_ptr(), lda, M, a_labels.data_ptr(), _ptr(a_valid), _ptr(b), ldb, N, _ptr(b_labels), _ptr(b_valid),
+            b_row0, D), M
+
+
+def ident_best(a, a_labels, b=None, b_labels=None, *, mate_key, non_key, skipped, a_valid=None, b_valid=None,
+               b_row0=0):
+    """Pass 1 of the identification evaluation (prpe_ident_best, include/prpe.h): per probe row of
+    ``a`` [M, D] the largest candidate key among the rows of ``b`` [N, D] with the probe's label
+    (``mate_key``) and among the others (``non_key``), both int64 [M] holding the uint64 keys,
+    raised by atomic maxima: the caller zeroes them. ``b`` None: leave-one-out on ``a``.
+    ``b_row0``: the number of ``b``'s first row, for a gallery passed in several ranges. ``skipped``
+    int64 [1] is ADDED the combinations whose score is not finite. Rows are already normalised
+    (``gallery_enrol``'s output). No host read."""
+    what = "prpe_ident_best"
+    args, M = _ident_operands(what, a, a_labels, b, b_labels, a_valid, b_valid, b_row0)
+    _check_dev(what, "mate_key", mate_key, torch.int64, (M,))
+    _check_dev(what, "non_key", non_key, torch.int64, (M,))
+    _check_dev(what, "skipped", skipped, torch.int64, (1,))
+    check(lib().prpe_ident_best(*args, mate_key.data_ptr(), non_key.data_ptr(), skipped.data_ptr(), _stream()), what)
+    return mate_key, non_key, skipped
+
+
+def ident_rank(a, a_labels, b=None, b_labels=None, *, mate_key, rank_minus_1, a_valid=None, b_valid=None, b_row0=0):
+    """Pass 2 (prpe_ident_rank): with ``mate_key`` of the whole gallery from ``ident_best``,
+    ``rank_minus_1`` int32 [M] is ADDED the number of non-mate candidates ahead of each probe's best
+    mate; the caller zeroes it. The operands are ``ident_best``'s. No host read."""
+    what = "prpe_ident_rank"
+    args, M = _ident_operands(what, a, a_labels, b, b_labels, a_valid, b_valid, b_row0)
+    _check_dev(what, "mate_key", mate_key, torch.int64, (M,))
+    _check_dev(what, "rank_minus_1", rank_minus_1, torch.int32, (M,))
+    check(lib().prpe_ident_rank(*args, mate_key.data_ptr(), rank_minus_1.data_ptr(), _stream()), what)
+    return rank_minus_1
+
+
+def ident_finish(a_labels, *, mate_key, non_key, nbins, mate_score, mate_row, non_score, non_row, rank, hist, counts,
+                 rank_minus_1=None, rank_hist=None, a_valid=None):
+    """Decode and bin (prpe_ident_finish): writes mate_score / non_score float32 [M], mate_row /
+    non_row / rank int32 [M]; ADDS the probes to ``hist`` int64 [3, nbins] (right label, wrong
+    label, stranger named), ``rank_hist`` int64 [IDENT_RANKS + 1] and ``counts`` int64 [4] (mated,
+    non-mated, left out, without any candidate): the caller zeroes these. ``rank_minus_1`` and
+    ``rank_hist`` go together; without them ``rank`` is 1, 0 or -1 (above 1). No host read."""
+    what = "prpe_ident_finish"
+    if not (isinstance(a_labels, torch.Tensor) and a_labels.dim() == 1 and 1 <= a_labels.shape[0] <= PAIR_HIST_MAX_ROWS):
+        raise ValueError(f"{what}: a_labels must be [1..2^24]")
+    M = a_labels.shape[0]
+    nbins = int(nbins)
+    if nbins not in PAIR_HIST_BINS:
+        raise ValueError(f"{what}: nbins must be one of {PAIR_HIST_BINS}, got {nbins}")
+    _check_dev(what, "a_labels", a_labels, torch.int64, (M,))
+    if a_valid is not None:
+        _check_dev(what, "a_valid", a_valid, torch.uint8, (M,))
+    _check_dev(what, "mate_key", mate_key, torch.int64, (M,))
+    _check_dev(what, "non_key", non_key, torch.int64, (M,))
+    if (rank_minus_1 is None) != (rank_hist is None):
+        raise ValueError(f"{what}: rank_minus_1 and rank_hist go together")
+    if rank_minus_1 is not None:
+        _check_dev(what, "rank_minus_1", rank_minus_1, torch.int32, (M,))
+        _check_dev(what, "rank_hist", rank_hist, torch.int64, (IDENT_RANKS + 1,))
+    _check_dev(what, "mate_score", mate_score, torch.float32, (M,))
+    _check_dev(what, "non_score", non_score, torch.float32, (M,))
+    _check_dev(what, "mate_row", mate_row, torch.int32, (M,))
+    _check_dev(what, "non_row", non_row, torch.int32, (M,))
+    _check_dev(what, "rank", rank, torch.int32, (M,))
+    _check_dev(what, "hist", hist, torch.int64, (3, nbins))
+    _check_dev(what, "counts", counts, torch.int64, (4,))
+    check(lib().prpe_ident_finish(M, a_labels.data_ptr(), _ptr(a_valid), mate_key.data_ptr(), non_key.data_ptr(),
+                                  _ptr(rank_minus_1), nbins, mate_score.data_ptr(), mate_row.data_ptr(),
+                                  non_score.data_ptr(), non_row.data_ptr(), rank.data_ptr(), hist.data_ptr(),
+                                  _ptr(rank_hist), counts.data_ptr(), _stream()), what)
+    return hist, rank_hist, counts
