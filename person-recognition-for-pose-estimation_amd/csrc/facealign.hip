@@ -5,10 +5,10 @@
 //   size, onto the person's COCO keypoints 2, 1, 0 (right eye, left eye, nose), in fp64, from
 //   template to frame so nothing is inverted. The six coefficients go to the matched face's row of
 //   ``warp`` when the gates hold; the match is one-to-one, so no two threads write one row.
-// prpe_roi_warp(_u8) — prpe_roi_resize(_u8)'s launch, stores and max|y| (csrc/roi.h). A slot whose
-//   warp row is flagged samples the frame along the row's affine map instead of the window of
-//   crop_meta: both tap pairs change per pixel, so the column part of each coordinate is formed
-//   once per thread and the row part once per row. The flag is uniform across the workgroup.
+// prpe_roi_warp(_u8) — prpe_roi_resize(_u8)'s launch, stores and max|y|. A slot whose warp row is
+//   flagged samples the frame along the row's affine map instead of the window of crop_meta
+//   (roi_warp_kernel, csrc/roi.h: one instantiation per frame source; the NV12 entry point is in
+//   csrc/nv12.hip).
 #pragma clang fp contract(off)
 #include "roi.h"
 
@@ -76,46 +76,6 @@ __global__ __launch_bounds__(64) void face_align_fit_kernel(FitK p) {
   o[2] = af; o[3] = bf; o[4] = txf; o[5] = cf; o[6] = df; o[7] = tyf;
 }
 
-// the workgroup's rows along the affine map of the slot's warp row; returns the thread's max|v|
-template <typename T>
-__device__ __forceinline__ float warp_rows(const ResK<T>& p, const ResBlock& k, const float* wr) {
-  const double a = wr[2], b = wr[3], tx = wr[4], c = wr[5], d = wr[6], ty = wr[7];
-  const T* base = p.src + (int64_t)k.f * p.sn;
-  int64_t oc[3];
-  channel_offsets(p, oc);
-  float mx = 0.f;
-  for (int j = threadIdx.x; j < p.ow; j += RR_THREADS) {
-    const double xc = a * (j + 0.5) + tx, yc = c * (j + 0.5) + ty;      // the column's part
-    float* yo = k.ybase + (int64_t)j * p.ysw;
-#pragma unroll 4
-    for (int r = 0; r < k.rows; ++r) {
-      const double v = (k.i0 + r) + 0.5;
-      const Tap sx = tap_at(xc + b * v - 0.5, p.W), sy = tap_at(yc + d * v - 0.5, p.H);
-      const int64_t oa = (int64_t)(sx.ina ? sx.ia : 0) * p.sw, ob = (int64_t)(sx.inb ? sx.ib : 0) * p.sw;
-      const T* ra = base + (int64_t)(sy.ina ? sy.ia : 0) * p.sh;
-      const T* rb = base + (int64_t)(sy.inb ? sy.ib : 0) * p.sh;
-      mx = resize_pixel(p, ra, rb, oc, oa, ob, sx, sy, yo + (int64_t)r * p.ysh, mx);
-    }
-  }
-  return mx;
-}
-
-template <typename T>
-__global__ __launch_bounds__(RR_THREADS) void roi_warp_kernel(ResK<T> p) {
-  __shared__ float wmax[RR_THREADS / 64];
-  ResBlock k;
-  if (!resize_block(p, k)) return;
-  const float* wr = p.warp + (int64_t)k.slot * 8;
-  const float mx = __float_as_int(wr[0]) == 1 ? warp_rows(p, k, wr) : resize_window(p, k);
-  resize_amax(p, k.slot, mx, wmax);
-}
-
-template <typename T>
-int roi_warp_launch(const ResK<T>& p, int64_t blocks, void* stream) {
-  hipLaunchKernelGGL(roi_warp_kernel<T>, dim3((unsigned)blocks), dim3(RR_THREADS), 0, as_stream(stream), p);
-  return launch_status();
-}
-
 }  // namespace
 
 extern "C" int prpe_face_align_fit(const float* crop_meta_f, const int32_t* n_f, int32_t max_f, const int32_t* n_p,
@@ -137,22 +97,15 @@ extern "C" int prpe_face_align_fit(const float* crop_meta_f, const int32_t* n_f,
 
 extern "C" int prpe_roi_warp(const prpe_view* frames, const float* crop_meta, const int32_t* n_crops,
                              int32_t max_crops, const float* warp, const prpe_view* y, float* y_amax, void* stream) {
-  ResK<float> p{};
-  int64_t blocks;
-  if (!warp || !resize_args(p, frames, crop_meta, n_crops, max_crops, y, y_amax, blocks)) return PRPE_EINVAL;
-  p.warp = warp;
-  return roi_warp_launch(p, blocks, stream);
+  ResK<ViewSrc<float>> p{};
+  if (!view_src(p.s, frames, 0)) return PRPE_EINVAL;
+  return resize_run<true>(p, crop_meta, n_crops, max_crops, warp, nullptr, nullptr, y, y_amax, stream);
 }
 
 extern "C" int prpe_roi_warp_u8(const prpe_view_u8* frames, const float* crop_meta, const int32_t* n_crops,
                                 int32_t max_crops, const float* warp, const float* a, const float* b,
                                 int32_t swap_rb, const prpe_view* y, float* y_amax, void* stream) {
-  ResK<uint8_t> p{};
-  int64_t blocks;
-  if (!warp || !a || !b || !resize_args(p, frames, crop_meta, n_crops, max_crops, y, y_amax, blocks))
-    return PRPE_EINVAL;
-  p.warp = warp;
-  for (int c = 0; c < 3; ++c) { p.a[c] = a[c]; p.b[c] = b[c]; }
-  p.swap_rb = swap_rb ? 1 : 0;
-  return roi_warp_launch(p, blocks, stream);
+  ResK<ViewSrc<uint8_t>> p{};
+  if (!view_src(p.s, frames, swap_rb)) return PRPE_EINVAL;
+  return resize_run<true>(p, crop_meta, n_crops, max_crops, warp, a, b, y, y_amax, stream);
 }

@@ -1,15 +1,20 @@
 // Per-face identification, the stages between the face detector and the trunk, and the join of
 // identities to skeletons:
 //
-// prpe_roi_select     — prpe_crop_select (csrc/topdown.hip) with the output size, and so the
-//   window's aspect, as arguments: the same one-workgroup scan, the same list every run.
+// prpe_roi_select     — padded NMS output -> a compact crop list in (frame, row) order, the window's
+//   aspect taken from the output size (prpe_crop_select, csrc/topdown.hip, is this at 256 x 192).
+//   ONE 256-thread workgroup: each thread counts the rows its frame contributes, a block prefix
+//   sum over the frames (in chunks of 256) assigns the slots, so the list is the same on every
+//   run (no atomics). Window arithmetic in fp32 with contraction off: the host restatement
+//   (tests/test_topdown_host.py) gives the same bits.
 // prpe_roi_resize(_u8) — the hot kernel: bilinear resample of each window to the out_h x out_w
 //   interior of any zero-bordered NHWC4 buffer (the stem's, at 112 x 112), one 16-B store per
 //   pixel, with the slot's max|y| for the precision-3 stem. One 128-thread workgroup per
 //   (slot, 8 output rows); a thread owns the output columns tid, tid + 128, ..., so a column's
 //   source index, weight and bounds are formed once per thread and a row's once per row; the
 //   window is the same for the whole workgroup. At 112 columns the two waves store 1 KiB and 768 B,
-//   contiguous. Taps: 12 gathered loads per pixel through the view's strides (§5b).
+//   contiguous. The workgroup is csrc/roi.h's, one instantiation per frame source (csrc/frames.h);
+//   the NV12 entry points are in csrc/nv12.hip.
 // prpe_face_person_match — one wavefront per frame: head point per person, centre per face, the
 //   32 x 32 cost matrix in registers (lane = face f and persons (lane >> 5) + 2 t), greedy
 //   one-to-one assignment by a wave-wide minimum of (cost, person, face) keys. No workspace, no
@@ -22,6 +27,41 @@ namespace {
 using namespace roi;
 
 constexpr int MATCH_MAX = 32;                  // persons / faces per frame the match takes
+constexpr int SEL_THREADS = 256;
+
+struct SelK {
+  const float* dets; const int* counts; int B, max_det;
+  float thr, min_size, sx, sy, pad; int per_frame, max_crops;
+  int out_h, out_w;
+  float* meta; int* n_crops; int* status;
+};
+
+// the window of one detection row, or false when the row is skipped
+__device__ __forceinline__ bool window(const SelK& p, const float* d, float& x0, float& y0, float& w, float& h) {
+  const float x1 = d[0] * p.sx, y1 = d[1] * p.sy, x2 = d[2] * p.sx, y2 = d[3] * p.sy;
+  if (!(finitef(x1) && finitef(y1) && finitef(x2) && finitef(y2))) return false;
+  w = x2 - x1;
+  h = y2 - y1;
+  if (!(w >= p.min_size) || !(h >= p.min_size)) return false;
+  const float cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f;
+  const float a = (float)p.out_w / (float)p.out_h;
+  if (w > a * h) h = w / a; else w = h * a;
+  w *= p.pad;
+  h *= p.pad;
+  x0 = cx - 0.5f * w;
+  y0 = cy - 0.5f * h;
+  return finitef(w) && finitef(h) && finitef(x0) && finitef(y0);
+}
+
+// rows of frame b in the candidate prefix: the first rows with score >= thr, at most per_frame
+__device__ __forceinline__ int prefix(const SelK& p, int b) {
+  int c = p.counts[b];
+  c = c < p.max_det ? c : p.max_det;
+  c = c < p.per_frame ? c : p.per_frame;
+  int n = 0;
+  while (n < c && p.dets[((int64_t)b * p.max_det + n) * 6 + 4] >= p.thr) ++n;
+  return n;
+}
 
 __global__ __launch_bounds__(SEL_THREADS) void roi_select_kernel(SelK p) {
   __shared__ int scan[SEL_THREADS];
@@ -75,14 +115,6 @@ __global__ __launch_bounds__(SEL_THREADS) void roi_select_kernel(SelK p) {
     *p.n_crops = n;
     *p.status = flags_s | (total > p.max_crops ? 2 : 0);
   }
-}
-
-template <typename T>
-__global__ __launch_bounds__(RR_THREADS) void roi_resize_kernel(ResK<T> p) {
-  __shared__ float wmax[RR_THREADS / 64];
-  ResBlock k;
-  if (!resize_block(p, k)) return;
-  resize_amax(p, k.slot, resize_window(p, k), wmax);
 }
 
 struct MatchK {
@@ -210,12 +242,6 @@ __global__ __launch_bounds__(64) void face_person_match_kernel(MatchK p) {
   }
 }
 
-template <typename T>
-int roi_resize_launch(const ResK<T>& p, int64_t blocks, void* stream) {
-  hipLaunchKernelGGL(roi_resize_kernel<T>, dim3((unsigned)blocks), dim3(RR_THREADS), 0, as_stream(stream), p);
-  return launch_status();
-}
-
 }  // namespace
 
 extern "C" int prpe_roi_select(const float* dets, const int32_t* counts, int32_t B, int32_t max_det, float score_thr,
@@ -242,21 +268,17 @@ extern "C" int prpe_roi_select(const float* dets, const int32_t* counts, int32_t
 
 extern "C" int prpe_roi_resize(const prpe_view* frames, const float* crop_meta, const int32_t* n_crops,
                                int32_t max_crops, const prpe_view* y, float* y_amax, void* stream) {
-  ResK<float> p{};
-  int64_t blocks;
-  if (!resize_args(p, frames, crop_meta, n_crops, max_crops, y, y_amax, blocks)) return PRPE_EINVAL;
-  return roi_resize_launch(p, blocks, stream);
+  ResK<ViewSrc<float>> p{};
+  if (!view_src(p.s, frames, 0)) return PRPE_EINVAL;
+  return resize_run<false>(p, crop_meta, n_crops, max_crops, nullptr, nullptr, nullptr, y, y_amax, stream);
 }
 
 extern "C" int prpe_roi_resize_u8(const prpe_view_u8* frames, const float* crop_meta, const int32_t* n_crops,
                                   int32_t max_crops, const float* a, const float* b, int32_t swap_rb,
                                   const prpe_view* y, float* y_amax, void* stream) {
-  ResK<uint8_t> p{};
-  int64_t blocks;
-  if (!a || !b || !resize_args(p, frames, crop_meta, n_crops, max_crops, y, y_amax, blocks)) return PRPE_EINVAL;
-  for (int c = 0; c < 3; ++c) { p.a[c] = a[c]; p.b[c] = b[c]; }
-  p.swap_rb = swap_rb ? 1 : 0;
-  return roi_resize_launch(p, blocks, stream);
+  ResK<ViewSrc<uint8_t>> p{};
+  if (!view_src(p.s, frames, swap_rb)) return PRPE_EINVAL;
+  return resize_run<false>(p, crop_meta, n_crops, max_crops, nullptr, a, b, y, y_amax, stream);
 }
 
 extern "C" int prpe_face_person_match(const float* crop_meta_p, const int32_t* n_p, int32_t max_p,
