@@ -52,14 +52,24 @@ def _conv(sd, p, x, stride=1, padding=0, groups=1):
     return F.conv2d(x, sd[p + ".weight"], sd.get(p + ".bias"), stride, padding, 1, groups)
 
 
+def _tap(taps, name, x):
+    """Record the stage output ``x`` under ``name`` when the caller asked for taps (a dict the
+    stage functions fill in execution order; tests/test_stage_parity_host.py). NCHW, as computed."""
+    if taps is not None:
+        taps[name] = x
+    return x
+
+
 # ----------------------------------------------------------------------------- trunk
-def resnet50_trunk(sd, x, calib=None):
+def resnet50_trunk(sd, x, calib=None, taps=None):
     """MultiTaskResNetFeatureExtractor.forward (training/modify_models.py:427-437) over
     torchvision resnet50 v1.5 (modify_models.py:446): stem 7x7/2, maxpool 3/2,
-    bottlenecks [3,4,6,3], stride on the 3x3, BN eps 1e-5."""
+    bottlenecks [3,4,6,3], stride on the 3x3, BN eps 1e-5.
+    ``taps``: backbone.conv1 (stem conv + bn + relu), backbone.maxpool, backbone.layerL.B (each
+    of the 16 block outputs)."""
     p = "backbone"
-    x = F.relu(_bn(sd, p + ".bn1", _conv(sd, p + ".conv1", x, 2, 3), calib=calib))
-    x = F.max_pool2d(x, 3, 2, 1)
+    x = _tap(taps, p + ".conv1", F.relu(_bn(sd, p + ".bn1", _conv(sd, p + ".conv1", x, 2, 3), calib=calib)))
+    x = _tap(taps, p + ".maxpool", F.max_pool2d(x, 3, 2, 1))
     for li, (planes, blocks, stride) in enumerate(((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)), 1):
         for b in range(blocks):
             q = f"{p}.layer{li}.{b}"
@@ -70,7 +80,7 @@ def resnet50_trunk(sd, x, calib=None):
             idt = x
             if b == 0:
                 idt = _bn(sd, q + ".downsample.1", _conv(sd, q + ".downsample.0", x, s), calib=calib)
-            x = F.relu(o + idt)
+            x = _tap(taps, q, F.relu(o + idt))
     return x
 
 
@@ -139,10 +149,9 @@ def make_anchors(feats, strides, offset=0.5):    # yolopt/util.py:85-96
     return torch.cat(anchors), torch.cat(stride_t)
 
 
-def yolo_branch(sd, p, feat, stride=(0.0, 0.0, 0.0), calib=None):
-    """CustomYOLO.forward in eval mode (modify_models.py:76-106, 139-142) ->
-    Head eval decode (nn.py:255-270). Returns [B, 4+1, A] = (cx,cy,w,h)*stride, sigmoid(cls).
-    ``stride`` defaults to zeros: a fresh ``Head`` after ``modify_yolo`` (nn.py:238)."""
+def yolo_adapter(sd, p, feat, calib=None, taps=None):
+    """CustomYOLO's adapter and input normalisation (modify_models.py:76-86) -> the [B,3,160,160]
+    map the net reads. ``taps``: <p>.adapter (that map)."""
     a = p + ".adapter"
     x = F.silu(_bn(sd, a + ".1", _conv(sd, a + ".0", feat), calib=calib))
     x = F.interpolate(x, size=(160, 160), mode="bilinear", align_corners=True)
@@ -153,14 +162,22 @@ def yolo_branch(sd, p, feat, stride=(0.0, 0.0, 0.0), calib=None):
     x = F.silu(_bn(sd, a + ".17", _conv(sd, a + ".16", x, 1, 1), calib=calib))
     x = x - x.mean(dim=(2, 3), keepdim=True)                       # modify_models.py:84-86
     x = x / (x.std(dim=(2, 3), keepdim=True) + 1e-6)
-    x = torch.sigmoid(x)
-    return yolo_net(sd, p, x, stride, calib)
+    return _tap(taps, a, torch.sigmoid(x))
 
 
-def yolo_net(sd, p, x, stride=(0.0, 0.0, 0.0), calib=None):
+def yolo_branch(sd, p, feat, stride=(0.0, 0.0, 0.0), calib=None, taps=None):
+    """CustomYOLO.forward in eval mode (modify_models.py:76-106, 139-142) ->
+    Head eval decode (nn.py:255-270). Returns [B, 4+1, A] = (cx,cy,w,h)*stride, sigmoid(cls).
+    ``stride`` defaults to zeros: a fresh ``Head`` after ``modify_yolo`` (nn.py:238)."""
+    return yolo_net(sd, p, yolo_adapter(sd, p, feat, calib, taps), stride, calib, taps)
+
+
+def yolo_net(sd, p, x, stride=(0.0, 0.0, 0.0), calib=None, taps=None):
     """yolopt ``YOLO.forward`` in eval mode (nn.py:294-297: net -> fpn -> head) on NCHW input:
     the adapter's [B,3,160,160] (A = 525) or raw [B,3,640,640] frames (A = 8400, the config-2
-    micro-bench variant)."""
+    micro-bench variant).
+    ``taps``: <p>.yolo.fpn.P3 / .P4 / .P5 (the neck levels the head reads) and <p>.yolo.head.raw
+    ([B, 65, A], the head output before the DFL decode)."""
     n = p + ".yolo.net"
     x = _yc(sd, n + ".p1.0", x, 3, 2, calib=calib)
     x = _csp(sd, n + ".p2.1", _yc(sd, n + ".p2.0", x, 3, 2, calib=calib), False, calib)
@@ -177,6 +194,7 @@ def yolo_net(sd, p, x, stride=(0.0, 0.0, 0.0), calib=None):
     h = p + ".yolo.head"
     outs = []
     for i, xi in enumerate((p3, p4, p5)):
+        _tap(taps, f"{f}.P{i + 3}", xi)
         bx = _yc(sd, f"{h}.box.{i}.1", _yc(sd, f"{h}.box.{i}.0", xi, 3, calib=calib), 3, calib=calib)
         bx = _conv(sd, f"{h}.box.{i}.2", bx)
         c = xi.shape[1]
@@ -189,7 +207,7 @@ def yolo_net(sd, p, x, stride=(0.0, 0.0, 0.0), calib=None):
     anchors, strides = (t.transpose(0, 1) for t in make_anchors(outs, stride))
     b = outs[0].shape[0]
     no = outs[0].shape[1]
-    x = torch.cat([o.view(b, no, -1) for o in outs], 2)
+    x = _tap(taps, h + ".raw", torch.cat([o.view(b, no, -1) for o in outs], 2))
     box, cls = x.split((64, no - 64), 1)
     # DFL (nn.py:212-225): softmax over 16 bins, 1x1 conv with weight arange(16)
     aa = box.shape[2]
@@ -209,19 +227,27 @@ for _cin, _d, _n in ((64, 64, 3), (64, 128, 4), (128, 256, 14), (256, 512, 3)):
     _IR50_UNITS += [(_cin, _d, 2)] + [(_d, _d, 1)] * (_n - 1)
 
 
-def adaface_branch(sd, feat, calib=None):
+_IR50_GROUP_ENDS = (2, 6, 20, 23)         # the last unit of each of the four groups
+
+
+def adaface_branch(sd, feat, calib=None, taps=None):
     """CustomAdaFace.forward without labels (modify_models.py:288-297): adapter ->
-    IR-50 (libs/net_adaface.py:144-167, 322-337) -> (x/||x||, ||x||)."""
+    IR-50 (libs/net_adaface.py:144-167, 322-337) -> (x/||x||, ||x||).
+    ``taps``: ada_face.adapter.0 (the .2 PReLU's output, before the resample), .4 / .7 / .10 (the
+    three 112x112 convs, each after its PReLU), ada_face.adaface_model.input_layer, .body.2 / .6 /
+    .20 / .23 (the last unit of each IR-50 group), .output (the 512-vector before the
+    normalisation), ada_face.norm and ada_face.emb."""
     a = "ada_face.adapter"
     pr = lambda t, q: F.prelu(t, sd[q + ".weight"])
-    x = pr(_bn(sd, a + ".1", _conv(sd, a + ".0", feat), calib=calib), a + ".2")
+    x = _tap(taps, a + ".0", pr(_bn(sd, a + ".1", _conv(sd, a + ".0", feat), calib=calib), a + ".2"))
     x = F.interpolate(x, size=(112, 112), mode="bilinear", align_corners=True)
-    x = pr(_bn(sd, a + ".5", _conv(sd, a + ".4", x, 1, 1), calib=calib), a + ".6")
-    x = pr(_bn(sd, a + ".8", _conv(sd, a + ".7", x, 1, 1), calib=calib), a + ".9")
-    x = pr(_bn(sd, a + ".11", _conv(sd, a + ".10", x, 1, 1), calib=calib), a + ".12")
+    x = _tap(taps, a + ".4", pr(_bn(sd, a + ".5", _conv(sd, a + ".4", x, 1, 1), calib=calib), a + ".6"))
+    x = _tap(taps, a + ".7", pr(_bn(sd, a + ".8", _conv(sd, a + ".7", x, 1, 1), calib=calib), a + ".9"))
+    x = _tap(taps, a + ".10", pr(_bn(sd, a + ".11", _conv(sd, a + ".10", x, 1, 1), calib=calib), a + ".12"))
     m = "ada_face.adaface_model"
     x = pr(_bn(sd, m + ".input_layer.1", _conv(sd, m + ".input_layer.0", x, 1, 1), calib=calib),
            m + ".input_layer.2")
+    _tap(taps, m + ".input_layer", x)
     for i, (cin, d, st) in enumerate(_IR50_UNITS):
         p = f"{m}.body.{i}"
         if cin == d:
@@ -233,12 +259,14 @@ def adaface_branch(sd, feat, calib=None):
         r = pr(_bn(sd, p + ".res_layer.2", r, calib=calib), p + ".res_layer.3")
         r = _bn(sd, p + ".res_layer.5", _conv(sd, p + ".res_layer.4", r, st, 1), calib=calib)
         x = r + sc
+        if i in _IR50_GROUP_ENDS:
+            _tap(taps, p, x)
     x = _bn(sd, m + ".output_layer.0", x, calib=calib)
     x = x.reshape(x.shape[0], -1)            # Dropout(0.4) is identity in eval
     x = F.linear(x, sd[m + ".output_layer.3.weight"], sd[m + ".output_layer.3.bias"])
-    x = _bn(sd, m + ".output_layer.4", x, calib=calib)
-    norm = torch.norm(x, 2, 1, True)
-    return torch.div(x, norm), norm
+    x = _tap(taps, m + ".output", _bn(sd, m + ".output_layer.4", x, calib=calib))
+    norm = _tap(taps, "ada_face.norm", torch.norm(x, 2, 1, True))
+    return _tap(taps, "ada_face.emb", torch.div(x, norm)), norm
 
 
 # ----------------------------------------------------------------------------- ViTPose
@@ -246,18 +274,23 @@ def _ln(sd, p, x):
     return F.layer_norm(x, (x.shape[-1],), sd[p + ".weight"], sd[p + ".bias"], 1e-12)
 
 
-def vitpose_backbone(sd, pixel_values):
+_VIT_TAP_LAYERS = (0, 5, 11)
+
+
+def vitpose_backbone(sd, pixel_values, taps=None):
     """VitPoseForPoseEstimation.forward (site-packages transformers/models/vitpose/
     modeling_vitpose.py:190-278) with the simple decoder (:120-144); backbone
     modeling_vitpose_backbone.py:43-98 (embeddings), :100-182 (attention), :271-326
-    (layer), :380-438 (final LN). Returns heatmaps [B,17,64,48]."""
+    (layer), :380-438 (final LN). Returns heatmaps [B,17,64,48].
+    ``taps``: <backbone>.embeddings (patch embedding + position, [B, L, D]), .encoder.layer.0 / .5 /
+    .11, .layernorm (the final layer norm) and vit_pose.heatmaps."""
     v = "vit_pose.vit_pose.backbone"
     x = F.conv2d(pixel_values, sd[v + ".embeddings.patch_embeddings.projection.weight"],
                  sd[v + ".embeddings.patch_embeddings.projection.bias"], 16, 2)
     b = x.shape[0]
     x = x.flatten(2).transpose(1, 2)
     pos = sd[v + ".embeddings.position_embeddings"]
-    x = x + pos[:, 1:] + pos[:, :1]
+    x = _tap(taps, v + ".embeddings", x + pos[:, 1:] + pos[:, :1])
     nh, dh = 12, 64
     for i in range(12):
         L = f"{v}.encoder.layer.{i}"
@@ -275,21 +308,26 @@ def vitpose_backbone(sd, pixel_values):
         hn = _ln(sd, L + ".layernorm_after", x)
         hn = F.gelu(F.linear(hn, sd[L + ".mlp.fc1.weight"], sd[L + ".mlp.fc1.bias"]))
         x = F.linear(hn, sd[L + ".mlp.fc2.weight"], sd[L + ".mlp.fc2.bias"]) + x
-    x = _ln(sd, v + ".layernorm", x)
+        if i in _VIT_TAP_LAYERS:
+            _tap(taps, L, x)
+    x = _tap(taps, v + ".layernorm", _ln(sd, v + ".layernorm", x))
     x = x.permute(0, 2, 1).reshape(b, -1, 16, 12).contiguous()
     x = F.relu(x)
     x = F.interpolate(x, scale_factor=4.0, mode="bilinear", align_corners=False)
-    return F.conv2d(x, sd["vit_pose.vit_pose.head.conv.weight"], sd["vit_pose.vit_pose.head.conv.bias"], 1, 1)
+    return _tap(taps, "vit_pose.heatmaps", F.conv2d(x, sd["vit_pose.vit_pose.head.conv.weight"],
+                                                    sd["vit_pose.vit_pose.head.conv.bias"], 1, 1))
 
 
-def vitpose_adapter(sd, feat, calib=None):
-    """CustomVitPose.adapter (modify_models.py:352-374) -> pixel_values [B,3,256,192]."""
+def vitpose_adapter(sd, feat, calib=None, taps=None):
+    """CustomVitPose.adapter (modify_models.py:352-374) -> pixel_values [B,3,256,192].
+    ``taps``: vit_pose.adapter.0 (the .1 BN + GELU output, before the resample) and .4 / .7 / .10
+    (the three 256x192 convs, each after its GELU; .10 is pixel_values)."""
     a = "vit_pose.adapter"
-    x = F.gelu(_bn(sd, a + ".1", _conv(sd, a + ".0", feat), calib=calib))
+    x = _tap(taps, a + ".0", F.gelu(_bn(sd, a + ".1", _conv(sd, a + ".0", feat), calib=calib)))
     x = F.interpolate(x, size=(256, 192), mode="bilinear", align_corners=True)
-    x = F.gelu(_bn(sd, a + ".5", _conv(sd, a + ".4", x, 1, 1), calib=calib))
-    x = F.gelu(_bn(sd, a + ".8", _conv(sd, a + ".7", x, 1, 1), calib=calib))
-    x = F.gelu(_bn(sd, a + ".11", _conv(sd, a + ".10", x, 1, 1), calib=calib))
+    x = _tap(taps, a + ".4", F.gelu(_bn(sd, a + ".5", _conv(sd, a + ".4", x, 1, 1), calib=calib)))
+    x = _tap(taps, a + ".7", F.gelu(_bn(sd, a + ".8", _conv(sd, a + ".7", x, 1, 1), calib=calib)))
+    x = _tap(taps, a + ".10", F.gelu(_bn(sd, a + ".11", _conv(sd, a + ".10", x, 1, 1), calib=calib)))
     return x
 
 

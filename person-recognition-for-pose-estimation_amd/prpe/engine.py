@@ -298,6 +298,11 @@ class Engine:
         ``track``: raise the output's per-frame max|y| slots in a precision-3/4 component (off for
         an output no conv consumes, e.g. the IR-50 output layer's split-K GEMM)."""
         x, res = _act(x), res.t if isinstance(res, Act) else res
+        if x.epoch is not None and self._amax_epoch.get(x.epoch[0]) != x.epoch[1]:
+            # the component that wrote x's max|x| slots has re-zeroed its pool since (a later trunk
+            # call): the slots now bound some other tensor, so x is read as one without any (a
+            # precision-4 head would otherwise scale by them, as feat_prec's precision 3 would)
+            x = Act(x.t, planes=x.planes)
         B, H, W, _ = x.t.shape
         Ho = (H + 2 * p.pad - p.kh) // p.stride + 1
         Wo = (W + 2 * p.pad - p.kw) // p.stride + 1
